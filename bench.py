@@ -406,7 +406,12 @@ def parse_args():
     ap.add_argument("--print-workload-key", action="store_true", help="print the key PMC summaries of this command line are filed under, and exit")
     ap.add_argument("--dry-run", action="store_true",
                     help="rendezvous only (no GPU work): every rank joins the process group, barrier, max-over-ranks, one JSON line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float32 / float64, rank 0, at most "
+                         "64 MB in all: a larger output is written as a fixed, seeded sample of its elements, see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     preset = CONFIGS.get(args.config, {})
     args.batch = args.batch if args.batch is not None else preset.get("batch", 32)
     args.frames = args.frames if args.frames is not None else preset.get("frames", 1024)
@@ -634,6 +639,41 @@ def write_details(obj, path=None):
         return None
 
 
+DUMP_BUDGET_BYTES = 64 * 2 ** 20
+DUMP_SEED = 20240601
+
+
+def dump_outputs(outputs, out_dir, budget=DUMP_BUDGET_BYTES):
+    """--dump-outputs: what the timed path returned in its last step, one DIR/<name>.npy per array (floating -> float32, or float64 when wider;
+    integer / bool -> float64; scalars as 0-d arrays).  When the arrays together exceed `budget` bytes, every array keeps the same fraction of its
+    elements: a stratified sample of the flattened array (one element drawn from each of k equal slices, numpy PCG64 seeded by DUMP_SEED and the
+    name), written flat -- the same shapes give the same positions in every run, so two builds compare element for element."""
+    arrays = {}
+    for name, v in sorted(outputs.items()):
+        if v is None:
+            continue
+        t = v.detach() if torch.is_tensor(v) else torch.as_tensor(np.asarray(v, dtype=np.float64))      # (python floats: doubles)
+        dt = (torch.float64 if t.dtype == torch.float64 else torch.float32) if t.is_floating_point() else torch.float64
+        arrays[name] = (t, dt)
+    total = sum(t.numel() * (8 if dt == torch.float64 else 4) for t, dt in arrays.values())
+    frac = min(1.0, (budget - 4096 * len(arrays)) / total) if total else 1.0      # (4 KiB a file for the .npy header)
+    os.makedirs(out_dir, exist_ok=True)
+    written = []
+    for name, (t, dt) in arrays.items():
+        n = t.numel()
+        k = n if frac >= 1.0 else max(1, int(n * frac))
+        if k < n:
+            rng = np.random.default_rng([DUMP_SEED, sum(name.encode())])
+            starts = np.arange(k, dtype=np.int64) * n // k
+            ends = np.arange(1, k + 1, dtype=np.int64) * n // k
+            idx = starts + (rng.random(k) * (ends - starts)).astype(np.int64)
+            t = t.reshape(-1).index_select(0, torch.from_numpy(idx).to(t.device))
+        a = t.to(dt).cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        written.append(f"{name}{list(a.shape)}" + (f" (sample of {n})" if k < n else ""))
+    print(f"[bench] --dump-outputs {out_dir}: " + ", ".join(written), file=sys.stderr, flush=True)
+
+
 
 class InferenceWorkload:
     """One inference configuration of BASELINE.json (headline / 2 / 4 / 5): model, resident inputs, step()."""
@@ -691,11 +731,12 @@ class InferenceWorkload:
 def timed_run(step, steps, warmup, profile, barrier, nstreams=1):
     """warm-up, then `steps` timed steps between two barriers.  nstreams > 1: the steps -- independent batches -- go through visinger_amd.synth.StreamRotation,
     the product's own batch pipeline (consecutive batches on alternating HIP streams: batch i + 1's latency-bound transformers under batch i's generator);
-    the warm-up runs through the same rotation, so every stream's allocator pool is warm."""
+    the warm-up runs through the same rotation, at least one step per stream, so every stream's allocator pool is warm (torch's caching allocator keeps a
+    pool per stream: a stream's first step allocates its whole working set, several GB at the headline shape, and must not fall inside the timed region)."""
     from visinger_amd.ops import PROFILER
     from visinger_amd.synth import StreamRotation
     rot = StreamRotation(nstreams, timing=True) if nstreams > 1 else None
-    for i in range(warmup):
+    for i in range(max(warmup, nstreams) if rot else warmup):
         out = rot.run(step)[0] if rot else step()
     if rot:
         rot.join()
@@ -806,6 +847,8 @@ def main():
     if args.config == 3:
         line = train_line(B, T, args.dropout, args.math, args.steps, args.warmup, rank, world, dist, dev, barrier)
         if rank == 0:
+            if args.dump_outputs:
+                dump_outputs(line["losses_last_step"], args.dump_outputs)      # what training_step returned in the last timed step
             det = write_details({"line": line})
             print(compact_line(line, args.math, det), flush=True)
         if dist is not None:
@@ -830,6 +873,8 @@ def main():
     out_dev, dt, per_step, single = timed_pipeline(wl.step, args.steps, args.warmup, barrier, args.streams)
     wav = out_dev["wav_out"]
     assert wav.shape == (B, T * HOP) and bool(torch.isfinite(wav).all())
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(out_dev, args.dump_outputs)       # the last of the --steps steps `value` is timed on
     dt = max_over_ranks(dt, device=dev if backend == "nccl" else None)
     samples = B * world * T * HOP * args.steps
 

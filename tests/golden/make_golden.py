@@ -623,7 +623,49 @@ def gen_mel_processing():
     save("mel_processing", **arrays)
 
 
+def sha(*tensors):
+    """sha256 over the float32 bytes of `tensors` in order: pins the seeded weights / inputs a fixture was made from without storing them"""
+    import hashlib
+    h = hashlib.sha256()
+    for t in tensors:
+        h.update(np.ascontiguousarray(t.detach().cpu().numpy(), dtype=np.float32).tobytes())
+    return np.array(h.hexdigest())
+
+
+def gen_full_width():
+    """Production width (hidden 192, gin 256, 512 initial generator channels) for tests/test_oracle_vs_live_reference_cpu.py.  The weights
+    (~14 M parameters a generator) are NOT stored: the test rebuilds them with the same seeded `randomize` on the package's own modules, whose
+    state dicts match the reference's key for key, and checks them against the stored sha256; the inputs likewise."""
+    flow = randomize(ResidualCouplingBlock(192, 192, 5, 1, 4, gin_channels=256).eval(), 201, 0.5)
+    gen = randomize(Generator(192, "1", [3, 7, 11], [[1, 3, 5]] * 3, [8, 8, 2, 2], 512, [16, 16, 4, 4], gin_channels=256).eval(), 202)
+    gen300 = randomize(Generator(192, "1", [3, 7, 11], [[1, 3, 5]] * 3, [5, 5, 3, 2, 2], 512, [11, 11, 7, 4, 4], gin_channels=256).eval(), 203)
+    g = torch.Generator().manual_seed(7)
+    z = torch.randn(1, 192, 12, generator=g)
+    cond = torch.randn(1, 256, 1, generator=g)
+    mask = torch.ones(1, 1, 12)
+    mask[0, :, 10:] = 0
+    arrays = {"flow.sha": sha(*flow.state_dict().values()), "gen.sha": sha(*gen.state_dict().values()),
+              "gen300.sha": sha(*gen300.state_dict().values()), "in1.sha": sha(z, cond, mask),
+              "flow.fwd": flow(z, mask, g=cond, reverse=False), "flow.inv": flow(z, mask, g=cond, reverse=True),
+              "gen.y": gen(z, g=cond), "gen300.y": gen300(z, g=cond)}
+    g = torch.Generator().manual_seed(8)
+    x = torch.randn(2, 192, 70, generator=g)
+    mask = torch.ones(2, 1, 70)
+    mask[1, :, 50:] = 0
+    enc = randomize(RelativeEncoder(192, 768, 2, 4, kernel_size=9, gin_channels=1).eval(), 204)
+    cond = torch.randn(2, 1, 70, generator=g)
+    post = randomize(PosteriorEncoder(1025, 192, 192, 5, 1, 16, gin_channels=256).eval(), 205, 0.5)
+    spec = torch.randn(2, 1025, 70, generator=g).abs()
+    spk = torch.randn(2, 256, 1, generator=g)
+    with CaptureRandn() as cap:
+        zq, mu, logs = post(spec, mask, g=spk)
+    arrays.update({"enc.sha": sha(*enc.state_dict().values()), "post.sha": sha(*post.state_dict().values()), "in2.sha": sha(x, mask, cond, spec, spk),
+                   "enc.y": enc(x, mask, g=cond), "post.noise": cap.draws[0], "post.z": zq, "post.mu": mu, "post.logs": logs})
+    save("full_width", **arrays)
+
+
 if __name__ == "__main__":
+    gen_full_width()
     gen_mel_processing()
     gen_wavenet()
     gen_posterior()

@@ -61,3 +61,24 @@ def test_traffic_is_keyed_by_workload():
     assert r["traffic"] is None and r["mfma_executed"] is None and "noted_site" not in r["all_instances"]      # (and no ZeroDivisionError)
     r = bench.roofline_from_profile(prof, 0.01, 1, bench.HEADLINE_WORKLOAD)
     assert r["traffic"] > 0 and r["traffic_over_algorithmic"] == r["traffic"] / 1e8
+
+
+def test_dump_outputs_is_bounded_and_reproducible(tmp_path):
+    """--dump-outputs: every returned array as <name>.npy in float32 / float64, at most 64 MB in all; a larger output becomes the same seeded
+    sample in every run (what lets two builds be compared output for output)"""
+    import numpy as np
+    import torch
+    g = torch.Generator().manual_seed(3)
+    small = {"wav_out": torch.randn(4, 1000, generator=g), "f0_pred": torch.randn(4, 10, 2, generator=g).double(), "ids": torch.arange(5),
+             "loss": 1.25, "absent": None}
+    bench.dump_outputs(small, str(tmp_path / "s"))
+    got = {p.stem: np.load(p) for p in (tmp_path / "s").glob("*.npy")}
+    assert set(got) == {"wav_out", "f0_pred", "ids", "loss"}
+    assert got["wav_out"].dtype == np.float32 and np.array_equal(got["wav_out"], small["wav_out"].numpy())
+    assert got["f0_pred"].dtype == np.float64 and got["ids"].dtype == np.float64 and float(got["loss"]) == 1.25
+    big = {"wav_out": torch.randn(20, 1 << 20, generator=g)}        # 80 MB of float32
+    for d in ("a", "b"):
+        bench.dump_outputs(big, str(tmp_path / d))
+    a, b = np.load(tmp_path / "a" / "wav_out.npy"), np.load(tmp_path / "b" / "wav_out.npy")
+    assert np.array_equal(a, b) and (tmp_path / "a" / "wav_out.npy").stat().st_size <= bench.DUMP_BUDGET_BYTES
+    assert a.size > 0.75 * bench.DUMP_BUDGET_BYTES / 4 and np.isin(a[:1000], big["wav_out"].numpy().reshape(-1)).all()
