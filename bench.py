@@ -16,7 +16,15 @@ reference's strided rule (batch[rank::world], tasks/base.py:130-133), no data-pa
 process touches the GPU -- the reference spawns its ranks itself as well, utils/commons/trainer.py:117-138); under
 torch.distributed.run it takes RANK / LOCAL_RANK / WORLD_SIZE from the environment and refuses a WORLD_SIZE != N.
 
-Prints ONE JSON line on rank 0 (see the keys below).  `roofline` is for the dominant kernel (the implicit-GEMM conv
+A plain run (no `--full`) does only what the headline figure needs: set-up, warm-up, the timed steps, `--dump-outputs` when given, and
+ONE JSON line on rank 0 (metric / value / unit / higher_is_better / dtype / ms_per_step and the workload's description; with `--streams 1`,
+where the per-launch HIP events are part of the timed steps themselves, also `roofline`).  Everything that takes runs or CPU time of its own is
+behind `--full`: the single-stream pass `roofline` comes from under the default two-stream rotation, the CPU baselines and the oracle checks of
+the timed run, the flow log-det check, the other fp32-class engines, the reduced lines of BASELINE configs 2 / 3 / 5 (printed BEFORE the
+headline line: the last line of stdout is always the headline's), the launch census of the training step and the details file.
+`--no-cpu-baseline`, `--no-other-configs` and `--quick` drop parts of a `--full` run.
+
+Under `--full`, `roofline` is for the dominant kernel (the implicit-GEMM conv
 instance with the largest share of the step: a split-bf16 MFMA instance by default), from HIP events recorded around
 each of its launches inside the timed steps: `achieved` = ALGORITHMIC FLOPs (the conv's own 2*MAC) / time, `frac` =
 achieved / the stated peak; what the matrix pipe executes on top of that (6 bf16 cross products per fp32 product) is under
@@ -387,7 +395,11 @@ def parse_args():
                     help="a BASELINE.json configuration (sets batch / frames / hidden / math); 0 = the headline workload")
     ap.add_argument("--batch", type=int, default=None, help="utterances per GPU (default 32)")
     ap.add_argument("--frames", type=int, default=None, help="T_mel (default 1024)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline figure: the single-stream roofline pass, CPU baselines and oracle checks, the flow log-det check, the other "
+                         "fp32-class engines, the reduced lines of BASELINE configs 2 / 3 / 5 and the details file (off by default: a plain run times "
+                         "its steps, prints its line and exits)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines, the oracle checks and the other engines")
     ap.add_argument("--streams", type=int, default=2,
                     help="HIP streams the timed batches rotate over (visinger_amd.synth.StreamRotation; 1 = every batch on one stream, the rounds 1-5 measurement)")
     ap.add_argument("--ragged", action="store_true", help="SURVEY 8d ragged variant: item lengths ~ U{T/2..T}, tails masked (mel2ph = 0)")
@@ -401,8 +413,8 @@ def parse_args():
     ap.add_argument("--dropout", type=float, default=0.1, help="config 3: p_dropout of the transformers (reference config: 0.1)")
     ap.add_argument("--storage", default=None, choices=("f32", "bf16"),
                     help="element type of the generator's activations in HBM (bf16 only with --math bf16; default: bf16 for --config 5)")
-    ap.add_argument("--no-other-configs", action="store_true", help="default run: skip the reduced lines of BASELINE configs 2 / 3 / 5")
-    ap.add_argument("--quick", action="store_true", help="skip the torch-CPU baseline and the split-bf16 x6 engine legs (the fp32 MFMA engine stays)")
+    ap.add_argument("--no-other-configs", action="store_true", help="--full: skip the reduced lines of BASELINE configs 2 / 3 / 5")
+    ap.add_argument("--quick", action="store_true", help="--full: skip the torch-CPU baseline and the split-bf16 x6 engine legs (the fp32 MFMA engine stays)")
     ap.add_argument("--print-workload-key", action="store_true", help="print the key PMC summaries of this command line are filed under, and exit")
     ap.add_argument("--dry-run", action="store_true",
                     help="rendezvous only (no GPU work): every rank joins the process group, barrier, max-over-ranks, one JSON line")
@@ -775,15 +787,23 @@ STREAMS_NOTE = ("value / ms_per_step: consecutive batches through visinger_amd.s
                 "i's generator); roofline and single_stream: the same steps on ONE stream, where a kernel's HIP-event duration is its own")
 
 
-def timed_pipeline(step, steps, warmup, barrier, nstreams):
-    """(out, dt, per_step, single): the timed region `value` is quoted on, plus -- when it ran on more than one stream -- a second, single-stream pass of the
-    same steps with the per-kernel HIP events on (under two-stream overlap a kernel's event duration includes the other stream's work: not a roofline input)."""
+def timed_pipeline(step, steps, warmup, barrier, nstreams, full=True):
+    """(out, dt, per_step, single): the timed region `value` is quoted on, plus -- when it ran on more than one stream, under --full -- a second, single-stream
+    pass of the same steps with the per-kernel HIP events on (under two-stream overlap a kernel's event duration includes the other stream's work: not a
+    roofline input).  A plain run on more than one stream has no per-kernel records: has_kernel_records()."""
     if nstreams <= 1:
         out, dt, per_step = timed_run(step, steps, warmup, True, barrier)
         return out, dt, per_step, None
     out, dt, per_step = timed_run(step, steps, warmup, False, barrier, nstreams)
+    if not full:
+        return out, dt, per_step, None
     _, dt1, per1 = timed_run(step, steps, min(warmup, 3), True, barrier)
     return out, dt, per_step, {"ms_per_step": dt1 / steps * 1e3, "ms_per_step_stats": percentile_stats(per1), "dt": dt1}
+
+
+def has_kernel_records(single, nstreams):
+    """whether ops.PROFILER holds the per-launch records of a timed_pipeline() call: from its single-stream pass, or from the timed steps themselves on one stream"""
+    return single is not None or nstreams <= 1
 
 
 def other_config_line(config, dev, steps, warmup, barrier, with_cpu=True, nstreams=2):
@@ -845,23 +865,23 @@ def main():
         torch.cuda.synchronize()
 
     if args.config == 3:
-        line = train_line(B, T, args.dropout, args.math, args.steps, args.warmup, rank, world, dist, dev, barrier)
+        line = train_line(B, T, args.dropout, args.math, args.steps, args.warmup, rank, world, dist, dev, barrier, census=args.full)
         if rank == 0:
             if args.dump_outputs:
                 dump_outputs(line["losses_last_step"], args.dump_outputs)      # what training_step returned in the last timed step
-            det = write_details({"line": line})
+            det = write_details({"line": line}) if args.full else None
             print(compact_line(line, args.math, det), flush=True)
         if dist is not None:
             dist.barrier()
             dist.destroy_process_group()
         return
 
-    # BASELINE configs 3 / 2 / 5 of the default run FIRST (one compact line each, printed before the headline line -- the driver parses the last line of
+    # --full: BASELINE configs 3 / 2 / 5 FIRST (one compact line each, printed before the headline line -- the driver parses the last line of
     # stdout -- 10 timed steps each, 20 for the training step, after 6 warm-up steps).  They used to follow the headline's runs in the same process; the training
     # step, which is as much host- as device-bound, then read 87-90 ms where its own process reads 81-84 (seven default runs against nine of its own, round 5):
     # it goes first, before the CPU baselines have started their thread pools and the headline's ~10^5 launches have gone through the runtime.
     pre = {}
-    if world == 1 and rank == 0 and not args.no_cpu_baseline and args.config in (0, 4) and not args.no_other_configs:
+    if args.full and world == 1 and rank == 0 and not args.no_cpu_baseline and args.config in (0, 4) and not args.no_other_configs:
         for c in (3, 2, 5):
             oc = other_config_line(c, dev, 20 if c == 3 else 10, 6, barrier, nstreams=args.streams)
             oc["n_gpus"] = 1
@@ -870,7 +890,7 @@ def main():
 
     wl = InferenceWorkload(args.config, B, T, args.hidden, args.math, args.storage, args.hop, args.ragged, dev, rank, world)
     model, hp = wl.model, wl.hp
-    out_dev, dt, per_step, single = timed_pipeline(wl.step, args.steps, args.warmup, barrier, args.streams)
+    out_dev, dt, per_step, single = timed_pipeline(wl.step, args.steps, args.warmup, barrier, args.streams, args.full)
     wav = out_dev["wav_out"]
     assert wav.shape == (B, T * HOP) and bool(torch.isfinite(wav).all())
     if rank == 0 and args.dump_outputs:
@@ -894,12 +914,14 @@ def main():
             "dtype": wl.dtype_name(),
             "data": "synthetic",
             "config": dict(wl.describe(world), realtime_factor=samples / dt / SR, streams=args.streams),
-            "roofline": roofline_from_profile(PROFILER.summary(), single["dt"] if single else dt, args.steps, wl.workload_key()),
         }
+        if has_kernel_records(single, args.streams):
+            out["roofline"] = roofline_from_profile(PROFILER.summary(), single["dt"] if single else dt, args.steps, wl.workload_key())
         if single:
             out["single_stream"] = {"ms_per_step": single["ms_per_step"], "value": B * T * HOP * args.steps / single["dt"], "ms_per_step_stats": single["ms_per_step_stats"]}
             out["streams_note"] = STREAMS_NOTE.format(n=args.streams)
-        headline = world == 1 and not args.no_cpu_baseline and args.config in (0, 4)
+        checks = args.full and world == 1 and not args.no_cpu_baseline      # the legs that cost CPU time or timed runs of their own
+        headline = checks and args.config in (0, 4)
         if headline:
             # the CPU oracle on item 0 of the timed batch, the same graph: the reported baseline AND the checker of the timed run
             out["cpu_baseline"] = cpu_baseline(model, hp, wl.batch, wav_dev=wav, f0_dev=out_dev.get("f0_pred"))
@@ -908,10 +930,10 @@ def main():
                 out["cpu_baseline_torch"] = cpu_baseline(model, hp, wl.batch, backend="torch")
             out["flow_logdet"] = flow_logdet_check(model, dev)
             out["flow_logdet_rel_err"] = out["flow_logdet"]["rel_err"]
-        elif world == 1 and args.config == 2 and not args.no_cpu_baseline:
+        elif checks and args.config == 2:
             out["cpu_baseline"], wav_cpu = cpu_baseline_config2(model, hp, wl.c2_inputs)
             out["waveform_max_abs_err"] = float(np.abs(wav[:wav_cpu.shape[0]].double().cpu().numpy() - wav_cpu).max())
-        if world == 1 and args.math in ("split3", "split6") and not args.no_cpu_baseline:
+        if checks and args.math in ("split3", "split6"):
             # the same workload on the other fp32-class engines, same process, same weights, same --steps / --warmup: the exact-fp32 MFMA /
             # F(2,3) kernels (the strictly-same-precision number to hold the headline arithmetic against: VERDICT r3 weak #2) and, outside
             # --quick, the split-bf16 x6 engine that was the default of rounds 1-2 (error against fp64: DESIGN.md 4, tests/test_conv_split_gpu.py)
@@ -932,7 +954,7 @@ def main():
             if c in pre:
                 details["other_configs"][str(c)] = pre[c]
                 lines.append(compact_line(pre[c], CONFIGS[c].get("math", "split3")))
-        det = write_details(details)
+        det = write_details(details) if args.full else None
         for ln in lines:
             print(ln, flush=True)
         print(compact_line(out, args.math, det), flush=True)
@@ -941,12 +963,12 @@ def main():
         dist.destroy_process_group()
 
 
-def train_line(B, T, dropout, math, steps, warmup, rank, world, dist, dev, barrier):
+def train_line(B, T, dropout, math, steps, warmup, rank, world, dist, dev, barrier, census=True):
     """BASELINE config 3: one full GAN training step (generator pass + discriminator pass, both optimizers; under N > 1 ranks the
     stock DistributedDataParallel gradient all-reduce over RCCL) on synthetic B=16, T_mel=512, segment 32 frames, hop 256.
     -> the bench line (dict).  `roofline.step`: algorithmic FLOPs of one step -- every conv / attention launch of the forward, the
     grad-input launches and the weight-gradient launches, counted by ops.PROFILER in counting mode on one extra un-timed step (no
-    events: 6 000 launches per step) -- over the measured step time."""
+    events: 6 000 launches per step) -- over the measured step time; without `census` (a plain run) the extra step and `roofline` are left out."""
     from visinger_amd import _lib as L
     from visinger_amd.dp import max_over_ranks
     from visinger_amd.models.visinger import hop256_hparams
@@ -972,16 +994,8 @@ def train_line(B, T, dropout, math, steps, warmup, rank, world, dist, dev, barri
         logs = tr.training_step(batch, runner=runner)
     barrier()
     dt = max_over_ranks(time.perf_counter() - t0, device=dev if dist is not None else None)
-    PROFILER.start(count_only=True)
-    tr.training_step(batch, runner=runner)
-    torch.cuda.synchronize()
-    PROFILER.stop()
-    counts = PROFILER.counts()
-    step_flops = sum(v["flops"] for v in counts.values())
-    step_tflops = step_flops / (dt / steps) / 1e12
     assert all(np.isfinite(v) for v in logs.values()), logs
-    peak = BF16_MFMA_PEAK_TFLOPS / MATH[math] if math in ("split3", "split6") else (FP32_MFMA_PEAK_TFLOPS if math == "f32" else BF16_MFMA_PEAK_TFLOPS)
-    return {
+    line = {
         "metric": "GAN training steps/sec (BASELINE config 3: posterior + flow fwd + MRF + MPD/MSD, both optimizer passes)",
         "value": steps * world / dt, "unit": "global steps/s (x n_gpus batches of B)", "n_gpus": world, "steps": steps,
         "warmup": warmup, "ms_per_step": dt / steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
@@ -990,19 +1004,30 @@ def train_line(B, T, dropout, math, steps, warmup, rank, world, dist, dev, barri
                                "generator + MPD/MSD, AdamW x2, random-init weights", "baseline_config": 3, "p_dropout": dropout, "per_gpu_batch": B,
                    "global_batch": B * world, "t_mel": T, "parallelism": f"dp{world} (DDP gradient all-reduce over RCCL)",
                    "vs_source_hash": library_source_hash()},
-        "roofline": {"bound": "mfma", "unit": "TFLOP/s", "achieved": step_tflops, "peak": peak, "frac": step_tflops / peak,
-                     "frac_vs_fp32_mfma_peak": step_tflops / FP32_MFMA_PEAK_TFLOPS,
-                     "traffic": (pmc_step_traffic(workload_key(3, B, T, 192, 256, "f32")) or {}).get("bytes_per_step"),
-                     "traffic_source": (pmc_step_traffic(workload_key(3, B, T, 192, 256, "f32")) or {}).get("source"),
-                     "step": {"algorithmic_tflop_per_step": step_flops / 1e12,
-                              "by_kind_tflop": {k: v["flops"] / 1e12 for k, v in sorted(counts.items(), key=lambda kv: -kv[1]["flops"])[:12]},
-                              "launches_counted": sum(v["launches"] for v in counts.values())},
-                     "note": "whole step (no single dominant kernel: 6 000 launches): algorithmic FLOPs (2*MAC) of every conv / attention "
-                             "launch of the forward, the grad-input launches and the weight-gradient launches (library GEMMs of the 1x1 / "
-                             "wide discriminator weight gradients included at their 2*MAC), counted on one extra step, / measured step time; "
-                             f"peak = the roof of the arithmetic ({peak:.0f} TFLOP/s: dense f16 / bf16 MFMA peak over the cross products per fp32 product of --math {math})"},
         "generated_samples_per_s": B * world * tr.segment_size * tr.hop * steps / dt,
         "losses_last_step": logs}
+    if not census:
+        return line
+    PROFILER.start(count_only=True)
+    tr.training_step(batch, runner=runner)
+    torch.cuda.synchronize()
+    PROFILER.stop()
+    counts = PROFILER.counts()
+    step_flops = sum(v["flops"] for v in counts.values())
+    step_tflops = step_flops / (dt / steps) / 1e12
+    peak = BF16_MFMA_PEAK_TFLOPS / MATH[math] if math in ("split3", "split6") else (FP32_MFMA_PEAK_TFLOPS if math == "f32" else BF16_MFMA_PEAK_TFLOPS)
+    line["roofline"] = {"bound": "mfma", "unit": "TFLOP/s", "achieved": step_tflops, "peak": peak, "frac": step_tflops / peak,
+                        "frac_vs_fp32_mfma_peak": step_tflops / FP32_MFMA_PEAK_TFLOPS,
+                        "traffic": (pmc_step_traffic(workload_key(3, B, T, 192, 256, "f32")) or {}).get("bytes_per_step"),
+                        "traffic_source": (pmc_step_traffic(workload_key(3, B, T, 192, 256, "f32")) or {}).get("source"),
+                        "step": {"algorithmic_tflop_per_step": step_flops / 1e12,
+                                 "by_kind_tflop": {k: v["flops"] / 1e12 for k, v in sorted(counts.items(), key=lambda kv: -kv[1]["flops"])[:12]},
+                                 "launches_counted": sum(v["launches"] for v in counts.values())},
+                        "note": "whole step (no single dominant kernel: 6 000 launches): algorithmic FLOPs (2*MAC) of every conv / attention "
+                                "launch of the forward, the grad-input launches and the weight-gradient launches (library GEMMs of the 1x1 / "
+                                "wide discriminator weight gradients included at their 2*MAC), counted on one extra step, / measured step time; "
+                                f"peak = the roof of the arithmetic ({peak:.0f} TFLOP/s: dense f16 / bf16 MFMA peak over the cross products per fp32 product of --math {math})"}
+    return line
 
 
 if __name__ == "__main__":

@@ -82,3 +82,24 @@ def test_dump_outputs_is_bounded_and_reproducible(tmp_path):
     a, b = np.load(tmp_path / "a" / "wav_out.npy"), np.load(tmp_path / "b" / "wav_out.npy")
     assert np.array_equal(a, b) and (tmp_path / "a" / "wav_out.npy").stat().st_size <= bench.DUMP_BUDGET_BYTES
     assert a.size > 0.75 * bench.DUMP_BUDGET_BYTES / 4 and np.isin(a[:1000], big["wav_out"].numpy().reshape(-1)).all()
+
+
+def test_full_is_an_option_and_off_by_default(monkeypatch):
+    """a plain command line asks for the headline figure alone; --full switches the other legs on, and the flags that trim them stay accepted"""
+    monkeypatch.setattr("sys.argv", ["bench.py", "--gpus", "1", "--steps", "4", "--warmup", "2"])
+    a = bench.parse_args()
+    assert a.full is False and (a.gpus, a.steps, a.warmup, a.streams, a.math, a.batch, a.frames) == (1, 4, 2, 2, "split3", 32, 1024)
+    monkeypatch.setattr("sys.argv", ["bench.py", "--full", "--quick", "--no-other-configs", "--no-cpu-baseline"])
+    a = bench.parse_args()
+    assert a.full is True and a.quick and a.no_other_configs and a.no_cpu_baseline
+    assert bench.has_kernel_records(None, 1) and not bench.has_kernel_records(None, 2) and bench.has_kernel_records({"dt": 1.0}, 2)
+
+
+def test_a_line_without_the_full_legs_is_still_the_headline_record():
+    """a plain run's record has no roofline / cpu_baseline / details: the compact line carries the contract keys and nothing invented"""
+    full = _full_r03()
+    plain = {k: v for k, v in full.items() if k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
+                                                    "vs_baseline", "dtype", "data", "config")}
+    d = json.loads(bench.compact_line(plain, "split3", None))
+    assert d["value"] == json.loads(bench.compact_line(full, "split3", None))["value"] and d["ms_per_step"] > 0 and d["higher_is_better"] is True
+    assert d["dtype"] == bench.SHORT_DTYPE["split3"] and not {"roofline", "cpu_baseline", "details", "fp32_mfma_engine"} & set(d)

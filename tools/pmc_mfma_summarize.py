@@ -5,7 +5,7 @@
 
 <pass_dir> holds *_counter_collection.csv and *_kernel_trace.csv of
     rocprofv3 --pmc SQ_INSTS_VALU_MFMA_MOPS_BF16 SQ_INSTS_VALU_MFMA_MOPS_F16 SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_INST_ANY \\
-              GRBM_GUI_ACTIVE --kernel-trace --output-format csv -- python3 bench.py --steps 1 --warmup 1 --no-cpu-baseline"""
+              GRBM_GUI_ACTIVE --kernel-trace --output-format csv -- python3 bench.py --full --steps 1 --warmup 1 --no-cpu-baseline"""
 import collections
 import csv
 import glob
@@ -46,7 +46,7 @@ def main():
                     dur[k] += kt.get(r["Dispatch_Id"], 0)
                     cnt[k] += 1
     out = {"source": "rocprofv3 --pmc SQ_INSTS_VALU_MFMA_MOPS_BF16 SQ_INSTS_VALU_MFMA_MOPS_F16 SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_INST_ANY "
-                     "GRBM_GUI_ACTIVE --kernel-trace --output-format csv -- python3 bench.py --steps 1 --warmup 1 --no-cpu-baseline (its own "
+                     "GRBM_GUI_ACTIVE --kernel-trace --output-format csv -- python3 bench.py --full --steps 1 --warmup 1 --no-cpu-baseline (its own "
                      "pass); mfma_tflops_executed = (SQ_INSTS_VALU_MFMA_MOPS_BF16 + _F16) x 512 FLOP / kernel time (one v_mfma_f32_32x32x16_bf16 = "
                      "64 MOPS = 32768 FLOP); mfma_pipe_util = SQ_VALU_MFMA_BUSY_CYCLES / (1024 SIMDs x GRBM_GUI_ACTIVE / 8 XCDs); "
                      "gfx_clock_ghz = GRBM_GUI_ACTIVE / 8 / kernel time", "kernels": {}}

@@ -63,7 +63,7 @@ def main():
             d = per.setdefault(short(k), {"fetch": [0, 0.0], "write": [0, 0.0]})
             d[field][0] += n
             d[field][1] += tot * 1024.0
-    out = {"source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) --kernel-trace -- python3 bench.py --steps 1 "
+    out = {"source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) --kernel-trace -- python3 bench.py --full --steps 1 "
                      "--warmup 1 --no-cpu-baseline; FETCH_SIZE doubled as MI355X_MICROARCH.md prescribes for gfx950 (calibration "
                      "in profiles/README.md: x0.53 for 16-B-per-lane streams, x0.70-0.76 for the 4-B-per-lane staging loads, so "
                      "the doubled figure is an upper bound)", "kernels": {}}
