@@ -218,7 +218,7 @@ def test_conv_handles_survive_copy_and_pickle():
     from visinger_amd.modules.rel_transformer import MultiHeadAttention, RelativeEncoder
     enc = RelativeEncoder(16, 32, 2, 1, kernel_size=3)
     att = enc.attn_layers[0]
-    att.__dict__["_hip_qkv_inf"] = (("key",), op, torch.zeros(1), torch.zeros(1))
+    att.__dict__["_hip_qkv_inf"] = op
     att.__dict__["_hip_qkv"] = object()
     att.conv_q.weight.data.mul_(2.0)                                 # the edit the cache key cannot see
     a2 = pickle.loads(pickle.dumps(att))

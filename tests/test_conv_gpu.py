@@ -352,3 +352,51 @@ def test_resblock_pair_fused_launch(oracle, C, k, d, T, B, math):
     acc_t = dev(accb)
     respair_forward(op1, op2, xd, acc_t, res=xd, acc=acc_t, scale=1.0 / 3.0)       # in-place accumulate, MRF average
     close(acc_t, (ref + accb) / 3.0, tol)
+
+
+def test_bind_is_keyed_and_the_paired_pack_equals_two_packs(monkeypatch):
+    """ConvOp.bind: a handle that carries `key` neither derives nor packs; key None packs every time; invalidate() makes the same key pack
+    again; and the paired pack (a conv + the VS_CONV_ADJOINT handle of its grad-input from one weight) leaves both handles with the
+    bytes and the key of two separate binds.  16 -> 32 channels, k = 3: the smallest conv on the 16-channel chunk path."""
+    from visinger_amd.ops import ConvOp
+    k, d, p = 3, 1, 1
+    g = torch.Generator().manual_seed(11)
+    w = (torch.randn(32, 16, k, generator=g) / np.sqrt(16 * k)).cuda()
+    b = torch.randn(32, generator=g).cuda()
+    x, gy = torch.randn(2, 16, 64, generator=g).cuda(), torch.randn(2, 32, 64, generator=g).cuda()
+    derived, packs, pack = [0], [0], ConvOp._pack
+
+    def counting(self, *args):
+        packs[0] += 1
+        return pack(self, *args)
+
+    def derive():
+        derived[0] += 1
+        return w, None, b
+
+    def handles():
+        return ConvOp(L.CONV1D, 16, 32, k, d, p), ConvOp(L.CONV1D, 32, 16, k, d, d * (k - 1) - p, L.CONV_ADJOINT)
+
+    monkeypatch.setattr(ConvOp, "_pack", counting)
+    key = (("w", 0), ("b", 0))
+    op, adj = handles()
+    assert op.bind(key, derive) is True and op.bind(key, derive) is False
+    assert (derived[0], packs[0]) == (1, 1) and op.has_weights_of(key)
+    assert adj.bind(key, lambda: (w, None, None)) is True and packs[0] == 2
+    y, gx = op.forward(x), adj.forward(gy)
+    close(y, torch.nn.functional.conv1d(x.cpu().double(), w.cpu().double(), b.cpu().double(), padding=p))
+    close(gx, torch.nn.functional.conv_transpose1d(gy.cpu().double(), w.cpu().double(), padding=p))
+
+    op2, adj2 = handles()
+    assert op2.bind(key, derive, adjoint=adj2) is True and (derived[0], packs[0]) == (2, 3)      # one pack call for the pair
+    assert op2.has_weights_of(key) and adj2.has_weights_of(key)
+    assert op2.bind(key, derive, adjoint=adj2) is False and adj2.bind(key, derive) is False and derived[0] == 2
+    assert torch.equal(op2.forward(x), y) and torch.equal(adj2.forward(gy), gx)
+
+    assert op.bind(None, derive) is True and op.bind(None, derive) is True                       # no key: packs every time
+    assert (derived[0], packs[0]) == (4, 5) and not op.has_weights_of(key) and not op.has_weights_of(None)
+    assert op.bind(key, derive) is True and op.bind(key, derive) is False
+    op.invalidate()
+    assert op.bind(key, derive) is True and (derived[0], packs[0]) == (6, 7)
+    assert torch.equal(op.forward(x), y)
+    torch.cuda.synchronize()

@@ -455,7 +455,7 @@ def test_training_transformer_layer_uses_the_streaming_attention(vs_option):
 
 
 def test_training_step_packs_each_weight_version_once(vs_option):
-    """ConvOp.set_weights_from / autograd.param_key: within one optimizer step the discriminators' convs see their (unchanged)
+    """ConvOp.bind / autograd.param_key: within one optimizer step the discriminators' convs see their (unchanged)
     parameters three times (real + generated batch in the generator pass, both in the discriminator pass) and every handle packs them
     once; after an optimizer step the versions differ and they are packed again.  The cached and the uncached run produce the SAME
     losses and parameters bit for bit (the packed bytes are identical), at fewer packs."""
@@ -473,17 +473,17 @@ def test_training_step_packs_each_weight_version_once(vs_option):
         g = torch.Generator().manual_seed(3)
         batch["noise_q"] = torch.randn(2, hp["hidden_size"], 48, generator=g).cuda()
         batch["u_slice"] = torch.rand(2, generator=g).cuda()
-        packs, orig = [0], ops.ConvOp.set_weights_from
+        packs, orig = [0], ops.ConvOp._pack
 
-        def counting(self, w, bias, key):
+        def counting(self, *args):
             packs[0] += 1
-            return orig(self, w, bias, key)
+            return orig(self, *args)
 
-        ops.ConvOp.set_weights_from = counting
+        ops.ConvOp._pack = counting
         try:
             logs = [tr.training_step(batch) for _ in range(3)]
         finally:
-            ops.ConvOp.set_weights_from = orig
+            ops.ConvOp._pack = orig
         return logs, packs[0], [p.detach().clone() for p in tr.parameters()]
 
     logs_c, packs_c, params_c = run(False)

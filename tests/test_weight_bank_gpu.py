@@ -78,7 +78,7 @@ def test_batch_pack_is_bit_identical_to_single_packs():
         a, s = ConvOp(kind, ci, co, k, d, p, flags), ConvOp(kind, ci, co, k, d, p, flags)
         a.set_math(math), s.set_math(math)
         jobs.append((a, w, b, ("k", len(jobs))))
-        s.set_weights_from(w, b, None)
+        s.bind(None, lambda: (w, None, b))
         singles.append(s)
         xs.append(torch.randn(2, ci, 300, device="cuda"))
     ConvOp.set_weights_batch(jobs)
@@ -90,7 +90,7 @@ def test_batch_pack_is_bit_identical_to_single_packs():
     jobs2 = [(a, w * 3.0, b, ("k2", i)) for i, (a, w, b, _) in enumerate(jobs)]
     ConvOp.set_weights_batch(jobs2)
     for (a, w, b, _), s, x in zip(jobs2, singles, xs):
-        s.set_weights_from(w, b, None)
+        s.bind(None, lambda: (w, None, b))
         assert torch.equal(a.forward(x), s.forward(x))
     ConvOp.set_weights_batch([])
     ConvOp.set_weights_batch(jobs2[:1])

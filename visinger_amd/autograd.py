@@ -37,7 +37,7 @@ def param_key(holder):
     """Identity and in-place versions of the PARAMETERS the live weight / bias of a conv holder derive from: (weight_v, weight_g) under
     torch.nn.utils.weight_norm, else the plain weight parameter; None when the weight is not a function of parameters alone (spectral
     norm runs a power iteration per forward).  Optimizer steps, load_state_dict and every other in-place write bump the versions; a
-    handle whose packed weights carry the same key need not be packed again (ConvOp.has_weights_of)."""
+    handle whose packed weights carry the same key need not be packed again (ConvOp.bind)."""
     if L.switch("VS_NO_PACK_CACHE"):
         return None
     sources = holder.__dict__.get("_key_sources")
@@ -66,19 +66,13 @@ class HipConvFn(torch.autograd.Function):
         x = x.contiguous().float()
         op = module._op(bind=False)
         key = param_key(module)
-        if not op.has_weights_of(key):
-            # the grad-input handle of a stride-1 conv (created by the first backward) takes the same weight: both packs in one pair of launches
-            adj = module.__dict__.get("_hip_bwd_ops", {}).get("dxa") if (key is not None and not L.switch("VS_NO_PAIR_PACK")) else None
-            if adj is not None and ctx.needs_input_grad[0]:
-                op.set_weights_pair(adj, w, b, key)
-            else:
-                op.set_weights_from(w, b, key)
+        op.bind(key, lambda: (w, None, b), _pair_adjoint(ctx, module, "_hip_bwd_ops", "dxa", key))
         if lrelu or res is not None:
             y = op.forward(x, in_act=L.IN_LRELU if lrelu else L.IN_NONE, res=None if res is None else res.contiguous().float())
         else:
             y = op.forward(x)
         ctx.module = module
-        ctx.wkey = key                  # the backward handles pack the adjoint of THIS weight: keyed by the forward's key, not by the parameters' state at backward time
+        ctx.wkey = key
         ctx.save_for_backward(x, w, b if b is not None else x.new_empty(0))
         ctx.has_bias = b is not None
         ctx.lrelu, ctx.has_res = bool(lrelu), res is not None
@@ -100,12 +94,21 @@ class HipConvFn(torch.autograd.Function):
         return gx, gw, gb, None, None, (gy if (ctx.has_res and need[5]) else None)
 
 
-def _bwd_op(module, key, *args):
-    """ConvOp handles of the backward-data convs, cached on the module next to the forward ones"""
-    ops = module.__dict__.setdefault("_hip_bwd_ops", {})
-    if key not in ops:
-        ops[key] = ConvOp(*args)
-    return ops[key]
+def _cached_op(holder, cache, name, *args):
+    """ConvOp handle `name` of `holder.__dict__[cache]` ("_hip_bwd_ops": the backward-data convs, next to a module's forward handles;
+    "_hip_disc_ops": the discriminator convs), created from `args` on first use"""
+    ops = holder.__dict__.setdefault(cache, {})
+    if name not in ops:
+        ops[name] = ConvOp(*args)
+    return ops[name]
+
+
+def _pair_adjoint(ctx, holder, cache, name, key):
+    """The grad-input handle `name` of `holder` (created by its first backward) when the forward's pack should fill it too -- the same weight,
+    both packs in one pair of launches (ConvOp.bind) -- else None"""
+    if key is None or L.switch("VS_NO_PAIR_PACK") or not ctx.needs_input_grad[0]:
+        return None
+    return holder.__dict__.get(cache, {}).get(name)
 
 
 def conv_backward(m, x, w, gy, need_x, need_w, key=False, need_b=None):
@@ -137,10 +140,8 @@ def conv_backward(m, x, w, gy, need_x, need_w, key=False, need_b=None):
             pb = d * (K - 1) - p
             assert pb >= 0, "conv backward-data: padding larger than the receptive field is not supported"
             # (the handle packs the adjoint -- channel transpose + tap reversal -- of the forward weight by index arithmetic)
-            op = _bwd_op(m, "dxa", L.CONV1D, Cout, Cin, K, d, pb, L.CONV_ADJOINT)
-            key = param_key(m) if key is False else key
-            if not op.has_weights_of(key):
-                op.set_weights_from(w, None, key)
+            op = _cached_op(m, "_hip_bwd_ops", "dxa", L.CONV1D, Cout, Cin, K, d, pb, L.CONV_ADJOINT)
+            op.bind(param_key(m) if key is False else key, lambda: (w, None, None))
             gx = op.forward(gy)
     else:
         Cout, u, p = w.shape[1], m.stride[0], m.padding[0]
@@ -152,11 +153,9 @@ def conv_backward(m, x, w, gy, need_x, need_w, key=False, need_b=None):
         gyp = F.pad(gy, (p, max(right, 0)))[:, :, :Mq * u]
         G = gyp.view(B, Cout, Mq, u).permute(0, 3, 1, 2).reshape(B, u * Cout, Mq)
         if need_x:
-            op = _bwd_op(m, "dx", L.CONV1D, u * Cout, Cin, Q, 1, 0, 0)
-            key = param_key(m) if key is False else key
-            if not op.has_weights_of(key):
-                wq = F.pad(w.detach(), (0, Q * u - K)).view(Cin, Cout, Q, u).permute(0, 3, 1, 2).reshape(Cin, u * Cout, Q)
-                op.set_weights_from(wq, None, key)
+            op = _cached_op(m, "_hip_bwd_ops", "dx", L.CONV1D, u * Cout, Cin, Q, 1, 0, 0)
+            op.bind(param_key(m) if key is False else key,
+                    lambda: (F.pad(w.detach(), (0, Q * u - K)).view(Cin, Cout, Q, u).permute(0, 3, 1, 2).reshape(Cin, u * Cout, Q), None, None))
             gx = op.forward(G.contiguous())                                             # [B, Cin, Mq - Q + 1 = T]
         if need_w:
             # gw2[ci, j, q] = sum_{b,m} x[b, ci, m] * G[b, j, m + q]: the same kernel with x in the role of the output gradient
@@ -168,13 +167,6 @@ def conv_backward(m, x, w, gy, need_x, need_w, key=False, need_b=None):
 
 # ------------------------------------------------------------------------------------------------------------------
 # discriminator convs: dense convs with a stride, and grouped strided convs
-
-
-def _cached_op(holder, key, *args):
-    ops_ = holder.__dict__.setdefault("_hip_disc_ops", {})
-    if key not in ops_:
-        ops_[key] = ConvOp(*args)
-    return ops_[key]
 
 
 def _phase_geometry(T, K, stride, pad):
@@ -213,19 +205,14 @@ class StridedConv1dFn(torch.autograd.Function):
         XF = torch.empty((1, stride * C, Lf + Q - 1), device=x.device, dtype=torch.float32)
         L.check(lib.vs_phase_stack(ctypes.c_void_p(x.data_ptr()), x.stride(0), x.stride(1), x.stride(2), L.ptr(XF), N, C, T, stride, pad, Hq,
                                    Lf + Q - 1, L.stream_ptr()))
-        op = _cached_op(holder, ("fwd", C, Cout, K, stride), L.CONV1D, stride * C, Cout, Q, 1, 0, 0)
+        op = _cached_op(holder, "_hip_disc_ops", ("fwd", C, Cout, K, stride), L.CONV1D, stride * C, Cout, Q, 1, 0, 0)
         key = param_key(holder)
-        if not op.has_weights_of(key):
-            wq = _phase_weights(w.detach(), stride, Q) if stride > 1 else w
-            adj = holder.__dict__.get("_hip_disc_ops", {}).get(("dxa", C, Cout, K, stride)) if (key is not None and not L.switch("VS_NO_PAIR_PACK")) else None
-            if adj is not None and ctx.needs_input_grad[0]:
-                op.set_weights_pair(adj, wq, b, key)
-            else:
-                op.set_weights_from(wq, b, key)
+        op.bind(key, lambda: (_phase_weights(w.detach(), stride, Q) if stride > 1 else w, None, b),
+                _pair_adjoint(ctx, holder, "_hip_disc_ops", ("dxa", C, Cout, K, stride), key))
         yF = op.forward(XF)                                                                     # [1, Cout, N*Hq]
         ctx.save_for_backward(XF, w)
         ctx.cfg = (N, C, T, K, stride, pad, Q, Hq, Tout, b is not None, holder)
-        ctx.wkey = key          # (the saved `w` is THIS version: the grad-input handle is labelled with it, as HipConvFn does -- ADVICE r4)
+        ctx.wkey = key
         return yF.view(Cout, N, Hq)[:, :, :Tout].permute(1, 0, 2)
 
     @staticmethod
@@ -251,10 +238,9 @@ class StridedConv1dFn(torch.autograd.Function):
                 g2 = conv_wgrad(gyF, XF, Q, 1, 0)                                               # [Cout, s*C, Q]
             gw = g2.view(Cout, stride, C, Q).permute(0, 2, 3, 1).reshape(Cout, C, Q * stride)[:, :, :K].contiguous() if stride > 1 else g2
         if ctx.needs_input_grad[0]:
-            op = _cached_op(holder, ("dxa", C, Cout, K, stride), L.CONV1D, Cout, stride * C, Q, 1, Q - 1, L.CONV_ADJOINT)
-            key = ctx.wkey      # (not param_key(holder) now: parameters stepped between forward and backward would label the OLD weight with the new key)
-            if not op.has_weights_of(key):      # (the handle packs the adjoint of the phase-stacked forward weight)
-                op.set_weights_from(_phase_weights(w.detach(), stride, Q) if stride > 1 else w, None, key)
+            op = _cached_op(holder, "_hip_disc_ops", ("dxa", C, Cout, K, stride), L.CONV1D, Cout, stride * C, Q, 1, Q - 1, L.CONV_ADJOINT)
+            # (the handle packs the adjoint of the phase-stacked forward weight)
+            op.bind(ctx.wkey, lambda: (_phase_weights(w.detach(), stride, Q) if stride > 1 else w, None, None))
             gXF = op.forward(gyF)                                                               # [1, s*C, N*Hq + Q - 1]
             gx = torch.empty((N, C, T), device=gy.device, dtype=torch.float32)
             L.check(lib.vs_phase_unstack(L.ptr(gXF), Lf + Q - 1, L.ptr(gx), N, C, T, stride, pad, Hq, L.stream_ptr()))

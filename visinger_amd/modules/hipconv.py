@@ -197,7 +197,7 @@ def repack_weights(module):
         for key in ("_hip_ops", "_hip_bwd_ops", "_hip_disc_ops"):
             for op in m.__dict__.get(key, {}).values():
                 op.invalidate()
-        for key in DERIVED_CACHES:      # caches keyed on (data_ptr, _version) of SEVERAL parameters: rebuilt from the live ones
+        for key in DERIVED_CACHES:      # handles keyed on (data_ptr, _version) of SEVERAL parameters: rebuilt from the live ones
             m.__dict__.pop(key, None)
     return module
 
@@ -208,7 +208,7 @@ DERIVED_CACHES = ("_hip_qkv_inf", "_hip_qkv")
 
 
 def drop_process_local_state(state):
-    """__getstate__ helper: remove conv handles and derived caches (device copies, ctypes handles) from a module's __dict__ copy"""
+    """__getstate__ helper: remove conv handles and derived caches (ctypes handles) from a module's __dict__ copy"""
     for key in ("_hip_ops", "_hip_bwd_ops", "_hip_disc_ops") + DERIVED_CACHES:
         state.pop(key, None)
     return state

@@ -117,7 +117,7 @@ class MultiHeadAttention(nn.Module):
             self.conv_k.bias.data.copy_(self.conv_q.bias.data)
         nn.init.xavier_uniform_(self.conv_v.weight)
 
-    def __getstate__(self):      # the fused q | k | v handle and its concatenated device copies are process-local caches
+    def __getstate__(self):      # the fused q | k | v handles are process-local caches
         return drop_process_local_state(self.__dict__.copy())
 
     def _fused_qkv_op(self):
@@ -129,16 +129,19 @@ class MultiHeadAttention(nn.Module):
         params = [t for cv in convs for t in (cv.weight, cv.bias)]
         math = self.conv_q._op(bind=False).math
         key = tuple((t.data_ptr(), t._version) for t in params) + (math,)
-        st = self.__dict__.get("_hip_qkv_inf")
-        if st is None or st[0] != key:
-            op = st[1] if st is not None else ConvOp(L.CONV1D, self.channels, 3 * self.channels, 1, 1, 0)
+        op = self.__dict__.get("_hip_qkv_inf")
+        if op is None:
+            op = self.__dict__["_hip_qkv_inf"] = ConvOp(L.CONV1D, self.channels, 3 * self.channels, 1, 1, 0)
+
+        def derive():
             if op.math != math:
                 op.set_math(math)
             w = torch.cat([cv.weight.detach() for cv in convs], 0).contiguous()
             b = torch.cat([cv.bias.detach() for cv in convs], 0).contiguous()
-            op.set_weights(w, None, b, force=True)
-            st = self.__dict__["_hip_qkv_inf"] = (key, op, w, b)
-        return st[1]
+            return w, None, b
+
+        op.bind(key, derive)
+        return op
 
     def forward(self, x, c, attn_mask=None, frame_mask=None, in_mask=False):
         """x, c: [B, C, T].  attn_mask: the reference's [B, 1, T, T] mask, which RelativeEncoder always builds as

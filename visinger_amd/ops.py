@@ -70,6 +70,37 @@ class LaunchProfiler:
 PROFILER = LaunchProfiler()
 
 
+def _launch(fn, *args):
+    """One C call `fn(*args)`.  -> None; with the profiler on, the (start, end) events recorded around the call on torch's current stream:
+    the caller appends (kernel instance, algorithmic flops, algorithmic HBM bytes) + events to PROFILER.records (the library names the
+    instance only after the launch)."""
+    if not PROFILER.enabled:
+        L.check(fn(*args))
+        return None
+    e0, e1 = PROFILER.events()
+    e0.record()
+    L.check(fn(*args))
+    e1.record()
+    return e0, e1
+
+
+def _conv_io(who, x, y, B, T, res=None, acc=None):
+    """-> (ConvIO, its out[0]) with x, B, T, y, res, acc and the dtypes filled in (vs_dtype in include/visinger_hip.h); res and acc follow y.
+    None for x / y: fp32, the pointer left to the caller."""
+    io = L.ConvIO()
+    io.x, io.x_dtype = L.act_ptr(x)
+    io.B, io.T = B, T
+    o = io.out[0]
+    o.y, io.y_dtype = L.act_ptr(y)
+    if res is not None or acc is not None:
+        for name, t in (("res", res), ("acc", acc)):
+            q, dt = L.act_ptr(t)
+            if t is not None and dt != io.y_dtype:
+                raise L.VisingerHipError(f"{who}: {name} is {t.dtype}, y is {torch.float32 if y is None else y.dtype}")
+            setattr(o, name, q)
+    return io, o
+
+
 class ConvOp:
     """vs_conv_t: one nn.Conv1d / nn.ConvTranspose1d site, weights folded + packed on the device."""
 
@@ -120,7 +151,7 @@ class ConvOp:
         return self
 
     def invalidate(self):
-        """Forget the packed-weight cache key: the next set_weights re-folds and re-packs.  For in-place edits the key cannot
+        """Forget the packed-weight cache key: the next set_weights / bind re-folds and re-packs.  For in-place edits the key cannot
         see (`p.data.copy_()` / `p.data.mul_()`: `.data` has its own version counter)."""
         self._wkey = None
 
@@ -161,42 +192,47 @@ class ConvOp:
     def rows_out(self):
         return self.c_out // 2 if self.kind == L.CONV1D_PAIRED else self.c_out
 
-    def set_weights(self, w, g=None, bias=None, force=False):
+    def set_weights(self, w, g=None, bias=None):
         """w: weight or weight_v; g: weight_g or None; bias or None (contiguous fp32 CUDA tensors).
-        Re-packs only when a tensor changed (data_ptr / in-place version) -- valid for PARAMETERS, whose storage persists;
-        callers that pass temporaries (the training path's folded weight: a new tensor every step, which the allocator
-        happily places at the previous step's address with version 0) must pass force=True."""
+        Re-packs only when a tensor changed (data_ptr / in-place version) -- valid for PARAMETERS, whose storage persists; temporaries
+        (the training path's folded weight: a new tensor every step, which the allocator happily places at the previous step's address
+        with version 0) go through bind() with a key of the parameters they derive from."""
         key = tuple((t.data_ptr(), t._version) if t is not None else None for t in (w, g, bias))
-        if key == self._wkey and not force:
-            return
-        w = w.detach()
-        g = None if g is None else g.detach()
-        bias = None if bias is None else bias.detach()
-        L.check(self.lib.vs_conv_set_weights(self.h, L.ptr(w.contiguous()), L.ptr(None if g is None else g.contiguous()),
-                                             L.ptr(None if bias is None else bias.contiguous()), L.stream_ptr()))
-        self._wkey = None if force else key
+        if key != self._wkey:
+            self.bind(key, lambda: (w, g, bias))
 
     def has_weights_of(self, key):
-        """True when the packed weights were derived from the parameters identified by `key` (set_weights_from)"""
+        """True when the packed weights were derived from the parameters identified by `key` (bind)"""
         return key is not None and key == self._wkey
 
-    def set_weights_from(self, w, bias, key):
-        """Training path: pack `w` / `bias`, TEMPORARIES derived from parameters identified by `key` = their (data_ptr, in-place version)
-        tuples (autograd.param_key), or None when the derivation is not a function of the parameters alone (spectral norm: a power
-        iteration per forward).  Within one optimizer step the same parameters reach a handle several times -- the discriminators see
-        the real and the generated batch in the generator pass and both again in the discriminator pass -- and every pack is one or
-        two launches + the weight's bytes: the caller asks has_weights_of(key) first and skips deriving `w` altogether."""
-        L.check(self.lib.vs_conv_set_weights(self.h, L.ptr(w.detach().contiguous()), None,
-                                             L.ptr(None if bias is None else bias.detach().contiguous()), L.stream_ptr()))
+    def bind(self, key, derive, adjoint=None):
+        """Pack the weights identified by `key` unless this handle already carries them.  -> True when it packed.
+        key: whatever identifies the PARAMETERS the weight derives from, compared by == -- autograd.param_key: their (data_ptr, in-place
+        version) tuples -- or None when nothing does (spectral norm: a power iteration per forward; VS_NO_PACK_CACHE): None always packs.
+        derive() -> (w, g, bias) as set_weights takes them, temporaries included; called only when the handle is stale, so the derivation
+        (a phase-stacked or concatenated weight) costs nothing otherwise.  Within one optimizer step the same parameters reach a handle
+        several times -- the discriminators see the real and the generated batch in the generator pass and both again in the
+        discriminator pass -- and every pack is one or two launches + the weight's bytes.
+        adjoint: the VS_CONV_ADJOINT handle of this conv's grad-input; it is packed from the same (folded: g is None) weight in the same
+        pair of launches (vs_conv_set_weights_pair) and carries `key` afterwards, so the backward finds its weights in place.  Staleness is
+        judged on this handle alone.
+        A backward binds its grad-input handle under the key its FORWARD computed (ctx.wkey), never under param_key at backward time:
+        the saved weight is the forward's version, and parameters stepped in between would label the old weight with the new key."""
+        if key is not None and key == self._wkey:
+            return False
+        self._pack(*derive(), adjoint)
         self._wkey = key
+        if adjoint is not None:
+            adjoint._wkey = key
+        return True
 
-    def set_weights_pair(self, adjoint_op, w, bias, key):
-        """Training path: pack `w` for this handle AND for the VS_CONV_ADJOINT handle of its grad-input in one pair of launches
-        (vs_conv_set_weights_pair); both carry `key` afterwards, so the backward finds its weights in place."""
-        L.check(self.lib.vs_conv_set_weights_pair(self.h, adjoint_op.h, L.ptr(w.detach().contiguous()),
-                                                  L.ptr(None if bias is None else bias.detach().contiguous()), L.stream_ptr()))
-        self._wkey = key
-        adjoint_op._wkey = key
+    def _pack(self, w, g, bias, adjoint=None):
+        w, g, bias = (None if t is None else t.detach().contiguous() for t in (w, g, bias))
+        if adjoint is not None:
+            assert g is None, "the paired pack takes a folded weight"
+            L.check(self.lib.vs_conv_set_weights_pair(self.h, adjoint.h, L.ptr(w), L.ptr(bias), L.stream_ptr()))
+        else:
+            L.check(self.lib.vs_conv_set_weights(self.h, L.ptr(w), L.ptr(g), L.ptr(bias), L.stream_ptr()))
 
     @staticmethod
     def set_weights_batch(jobs):
@@ -227,32 +263,23 @@ class ConvOp:
         if y is None and y_ptr is None:
             rows = split_row if split_row else self.rows_out
             y = torch.empty((B, rows, Tout), device=x.device, dtype=y_dtype or torch.float32)
-        io = L.ConvIO()
+        # (a raw pointer replaces its tensor: fp32, and nothing of that tensor is looked at)
+        io, o = _conv_io("ConvOp.forward", x if x_ptr is None else None, y if y_ptr is None else None, B, T,
+                         res if res_ptr is None else None, acc if acc_ptr is None else None)
         if x_ptr is not None:
             io.x = x_ptr
-        else:
-            io.x, io.x_dtype = L.act_ptr(x)
-        io.x_bs, io.B, io.T = x_bs, B, T
+        if y_ptr is not None:
+            o.y = y_ptr
+        if res_ptr is not None:
+            o.res = res_ptr
+        if acc_ptr is not None:
+            o.acc = acc_ptr
+        io.x_bs = x_bs
         io.in_act = in_act
         io.mask = L.ptr(mask)
         io.bias_b = L.ptr(bias_b)
         io.bias_b_bs = bias_b_bs
         io.split_row = split_row
-        o = io.out[0]
-        if y_ptr is not None:
-            o.y = y_ptr
-            o.res = res_ptr if res_ptr is not None else L.ptr(res)
-            o.acc = acc_ptr if acc_ptr is not None else L.ptr(acc)
-        else:
-            o.y, io.y_dtype = L.act_ptr(y)
-            for name, t, tp in (("res", res, res_ptr), ("acc", acc, acc_ptr)):
-                if tp is not None:
-                    setattr(o, name, tp)
-                else:
-                    q, dt = L.act_ptr(t)
-                    if t is not None and dt != io.y_dtype:
-                        raise L.VisingerHipError(f"ConvOp.forward: {name} is {t.dtype}, y is {y.dtype}")
-                    setattr(o, name, q)
         o.y_bs, o.res_bs, o.acc_bs = y_bs, res_bs, acc_bs
         o.scale, o.out_act, o.out_mask, o.mode = scale, out_act, int(bool(out_mask)), mode
         if out1 is not None:
@@ -265,18 +292,12 @@ class ConvOp:
             o1.out_mask, o1.mode = int(bool(out1.get("out_mask", False))), out1.get("mode", L.MODE_LINEAR)
         io.pair_mode = pair_mode
         io.logdet = L.ptr(logdet)
-        if PROFILER.enabled:
-            e0, e1 = PROFILER.events()
-            e0.record()
-            L.check(self.lib.vs_conv_forward(self.h, ctypes.byref(io), L.stream_ptr()))
-            e1.record()
-            self._last_kernel = self.last_kernel()
+        ev = _launch(self.lib.vs_conv_forward, self.h, ctypes.byref(io), L.stream_ptr())
+        self._last_kernel = self.last_kernel()
+        if ev:
             passes = 1 + (res is not None or res_ptr is not None) + (acc is not None or acc_ptr is not None)
             nb = B * ((2.0 if io.x_dtype else 4.0) * self.c_in * T + (2.0 if io.y_dtype else 4.0) * passes * self.rows_out * Tout)   # x once, residual / accumulate inputs once, y once
-            PROFILER.records.append((self._last_kernel, self.algorithmic_flops(B, T), nb, e0, e1))
-        else:
-            L.check(self.lib.vs_conv_forward(self.h, ctypes.byref(io), L.stream_ptr()))
-            self._last_kernel = self.last_kernel()
+            PROFILER.records.append((self._last_kernel, self.algorithmic_flops(B, T), nb) + ev)
         return y
 
 
@@ -322,18 +343,14 @@ def rel_attention(qkv, n_heads, rel_k=None, rel_v=None, mask=None, window_size=N
     # per query block (vs_relattn_fwd_work); 0 bytes: not applicable
     kv_bytes = int(lib.vs_relattn_kv_work_bytes(B, n_heads, C // n_heads, T, int(math)))
     kv_work = torch.empty((kv_bytes,), device=qkv.device, dtype=torch.uint8) if kv_bytes else None
-    if PROFILER.enabled:
-        e0, e1 = PROFILER.events()
-        e0.record()
-    L.check(lib.vs_relattn_fwd_work(_off(qkv, 0), _off(qkv, C * T), _off(qkv, 2 * C * T), C3 * T,
-                                    L.ptr(None if rel_k is None else rel_k.detach().contiguous()),
-                                    L.ptr(None if rel_v is None else rel_v.detach().contiguous()), L.ptr(mask), L.ptr(out),
-                                    C * T, B, n_heads, C // n_heads, T, ws, 1 if rel_k is None else rel_k.shape[0],
-                                    int(math), L.ptr(work), ksplit,
-                                    None if kv_work is None else ctypes.c_void_p(kv_work.data_ptr()), kv_bytes, L.stream_ptr()))
-    if PROFILER.enabled:
-        e1.record()      # algorithmic work: Q K^T and P V over the full [T, T] score matrix = 4 * T * T * k_channels per head
-        PROFILER.records.append((lib.vs_last_kernel_name().decode(), 4.0 * B * C * T * T, 4.0 * B * 4 * C * T, e0, e1))
+    ev = _launch(lib.vs_relattn_fwd_work, _off(qkv, 0), _off(qkv, C * T), _off(qkv, 2 * C * T), C3 * T,
+                 L.ptr(None if rel_k is None else rel_k.detach().contiguous()),
+                 L.ptr(None if rel_v is None else rel_v.detach().contiguous()), L.ptr(mask), L.ptr(out),
+                 C * T, B, n_heads, C // n_heads, T, ws, 1 if rel_k is None else rel_k.shape[0],
+                 int(math), L.ptr(work), ksplit,
+                 None if kv_work is None else ctypes.c_void_p(kv_work.data_ptr()), kv_bytes, L.stream_ptr())
+    if ev:      # algorithmic work: Q K^T and P V over the full [T, T] score matrix = 4 * T * T * k_channels per head
+        PROFILER.records.append((lib.vs_last_kernel_name().decode(), 4.0 * B * C * T * T, 4.0 * B * 4 * C * T) + ev)
     return out
 
 
@@ -527,27 +544,14 @@ def resblock_forward(ops, x, y, acc=None, scale=1.0):
     residual stream in registers between the pairs (csrc/resblock_f16.hip: split-f16 arithmetic on fp32 tensors, or plain bf16 operands on
     bf16-resident tensors)."""
     B, C, T = x.shape
-    io = L.ConvIO()
-    io.x, io.x_dtype = L.act_ptr(x)
-    io.x_bs, io.B, io.T = 0, B, T
+    io, o = _conv_io("resblock_forward", x, y, B, T, acc=acc)
     io.in_act = L.IN_LRELU
-    o = io.out[0]
-    o.y, io.y_dtype = L.act_ptr(y)
-    o.acc, adt = L.act_ptr(acc)
-    if acc is not None and adt != io.y_dtype:
-        raise L.VisingerHipError(f"resblock_forward: acc is {acc.dtype}, y is {y.dtype}")
     o.scale = scale
-    lib = ops[0].lib
-    if PROFILER.enabled:
-        e0, e1 = PROFILER.events()
-        e0.record()
-        L.check(lib.vs_resblock_forward(_handle_array(ops), len(ops), ctypes.byref(io), L.stream_ptr()))
-        e1.record()
-        nb = float(x.element_size()) * B * C * T * (2 + (acc is not None))
-        PROFILER.records.append((ops[0].last_kernel(), sum(op.algorithmic_flops(B, T) for op in ops), nb, e0, e1))
-    else:
-        L.check(lib.vs_resblock_forward(_handle_array(ops), len(ops), ctypes.byref(io), L.stream_ptr()))
+    ev = _launch(ops[0].lib.vs_resblock_forward, _handle_array(ops), len(ops), ctypes.byref(io), L.stream_ptr())
     name = ops[0].last_kernel()
+    if ev:
+        nb = float(x.element_size()) * B * C * T * (2 + (acc is not None))
+        PROFILER.records.append((name, sum(op.algorithmic_flops(B, T) for op in ops), nb) + ev)
     for op in ops:
         op._last_kernel = name
     return y
@@ -556,26 +560,12 @@ def resblock_forward(ops, x, y, acc=None, scale=1.0):
 def respair_forward(op1, op2, x, y, res=None, acc=None, scale=1.0):
     """a11: y = conv2(lrelu(conv1(lrelu(x)))) + res [+ acc] [* scale] in one launch (csrc/resblock_pair.hip)."""
     B, C, T = x.shape
-    io = L.ConvIO()
-    io.x, io.x_dtype = L.act_ptr(x)
-    io.x_bs, io.B, io.T = 0, B, T
+    io, o = _conv_io("respair_forward", x, y, B, T, res, acc)
     io.in_act = L.IN_LRELU
-    o = io.out[0]
-    o.y, io.y_dtype = L.act_ptr(y)
-    for name, t in (("res", res), ("acc", acc)):
-        q, dt = L.act_ptr(t)
-        if t is not None and dt != io.y_dtype:
-            raise L.VisingerHipError(f"respair_forward: {name} is {t.dtype}, y is {y.dtype}")
-        setattr(o, name, q)
     o.scale = scale
-    if PROFILER.enabled:
-        e0, e1 = PROFILER.events()
-        e0.record()
-        L.check(op1.lib.vs_respair_forward(op1.h, op2.h, ctypes.byref(io), L.stream_ptr()))
-        e1.record()
-        nb = (2.0 if io.y_dtype else 4.0) * B * C * T * (2 + (res is not None) + (acc is not None))
-        PROFILER.records.append((op1.last_kernel(), op1.algorithmic_flops(B, T) + op2.algorithmic_flops(B, T), nb, e0, e1))
-    else:
-        L.check(op1.lib.vs_respair_forward(op1.h, op2.h, ctypes.byref(io), L.stream_ptr()))
+    ev = _launch(op1.lib.vs_respair_forward, op1.h, op2.h, ctypes.byref(io), L.stream_ptr())
     op1._last_kernel = op2._last_kernel = op1.last_kernel()
+    if ev:
+        nb = (2.0 if io.y_dtype else 4.0) * B * C * T * (2 + (res is not None) + (acc is not None))
+        PROFILER.records.append((op1._last_kernel, op1.algorithmic_flops(B, T) + op2.algorithmic_flops(B, T), nb) + ev)
     return y
