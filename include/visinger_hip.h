@@ -38,7 +38,7 @@ VS_API const char *vs_last_error(void);
  * this library, so a caller that attributes per-launch timings to kernel instances (bench.py's roofline line) reads it back
  * here instead of restating the selection.  Thread-local; "" before the first launch.  (No reference counterpart.)          */
 VS_API const char *vs_last_kernel_name(void);
-VS_API int vs_abi_version(void);          /* 7: vs_conv_set_weights_batch, vs_weight_norm_multi_fwd / _bwd, vs_conv_wgrad_bias, vs_wn_step_fwd / _bwd, vs_l1_mean_fwd / _bwd; 6: vs_source_hash, vs_bias_grad, vs_conv_set_weights_pair; 5: vs_relattn_fwd_work / vs_relattn_kv_work_bytes; 4: vs_set_option / vs_get_option / vs_reset_option; 3: vs_dtype in vs_conv_io_t; 2: vs_relattn_fwd(math) */
+VS_API int vs_abi_version(void);          /* 7: vs_normal_fill, vs_prior_sample (appended to 7: new exports only, no layout or signature changed), vs_conv_set_weights_batch, vs_weight_norm_multi_fwd / _bwd, vs_conv_wgrad_bias, vs_wn_step_fwd / _bwd, vs_l1_mean_fwd / _bwd; 6: vs_source_hash, vs_bias_grad, vs_conv_set_weights_pair; 5: vs_relattn_fwd_work / vs_relattn_kv_work_bytes; 4: vs_set_option / vs_get_option / vs_reset_option; 3: vs_dtype in vs_conv_io_t; 2: vs_relattn_fwd(math) */
 /* sha256 (hex) over the sources this library was compiled from (kernels, headers, textual includes, the build recipe), embedded by
  * visinger_amd/csrc/build.py.  The loader recomputes it over the tree it sits in and refuses a library built from other sources (a
  * stale object that an mtime check would pass after a checkout).  (No reference counterpart: the reference has no native code.)  */
@@ -328,6 +328,26 @@ VS_API int vs_relattn_train_bwd(const float *q, const float *k, const float *v, 
  *     dy[b, F + f] = 2 y[b, F + f] dp[b, f].                                                                                      */
 VS_API int vs_spec_power_fwd(const float *y, float *p, int64_t B, int64_t F, int64_t T, void *stream);
 VS_API int vs_spec_power_bwd(const float *y, const float *dp, float *dy, int64_t B, int64_t F, int64_t T, void *stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * f3  seeded per-item sampling of the synthesis path.  No reference counterpart for the stream (the reference draws torch.randn_like, whose
+ *     values depend on the batch they are drawn in); vs_prior_sample replaces that draw plus the arithmetic of models/visinger.py:107,
+ *     z_p = (mu_p + randn_like(mu_p) * exp(logs_p)) * frame_mask, in one launch.
+ *     Stream: n(seed, take, c, t) from Philox4x32-10 with key (seed & 0xffffffff, seed >> 32) and counter (t, c >> 2, take, 0): the four
+ *     outputs give channels 4q .. 4q + 3 of frame t as two Box-Muller pairs (DESIGN.md "Seeded sampling").  A value depends on nothing else:
+ *     not on B, the row, the padded T, H or K.  seeds: DEVICE int64 [B], 0 <= seed < 2^63, read by the kernel (a captured graph is replayed
+ *     with other seeds by overwriting that buffer).
+ *     vs_normal_fill:  out [B * K, H, T], row b * K + k = take take0 + k of item b.
+ *     vs_prior_sample: z[b * K + k, c, t] = (mu[b, c, t] + noise_scale * n * exp(logs[b, c, t])) * mask[b, t]; mu / logs: rows of one
+ *                      [B, 2H, T] projection output (FramePriorNetwork.proj), batch stride stat_batch_stride in elements, row stride T;
+ *                      mask [B, T] or NULL (all ones), a masked frame is exactly 0; eps_out [B * K, H, T] or NULL: receives n, bit-identical
+ *                      to vs_normal_fill.
+ *     VS_EINVAL before anything is launched: NULL seeds / out / z / mu / logs, B, H, T <= 0, K < 1, take0 < 0, take0 + K > 2^32, T > 2^32,
+ *     stat_batch_stride < H * T.  One launch, no allocation, no host synchronisation.                                              */
+VS_API int vs_normal_fill(const int64_t *seeds, int64_t take0, int64_t K, float *out, int64_t B, int64_t H, int64_t T, void *stream);
+VS_API int vs_prior_sample(const float *mu, const float *logs, int64_t stat_batch_stride, const float *mask, const int64_t *seeds,
+                           int64_t take0, int64_t K, float noise_scale, float *z, float *eps_out, int64_t B, int64_t H, int64_t T,
+                           void *stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * a13 grouped / strided Conv1d of the scale discriminator (modules/discriminator.py:55-60) and its gradients.

@@ -9,13 +9,15 @@ reference's transpose restores the intended [B, 1, T]; with ``use_pitch_embed=Fa
 reference (and is parity-tested against its golden output).
 
 RNG: ``noise`` / ``noise_q`` / ``u_slice`` may be injected for reproducible parity (CPU and GPU generators differ);
-when omitted they are drawn exactly where the reference draws them.
+when omitted they are drawn exactly where the reference draws them.  ``seeds`` (synthesis only) draws the prior sample from per-item
+counter-based streams on the device instead (visinger_amd/sampling.py): an item's waveform then depends on (weights, item, seed) alone.
 """
 from copy import deepcopy
 
 import torch
 import torch.nn as nn
 
+from .. import sampling
 from ..modules.commons.utils import Embedding, rand_slice_segments, slice_segments
 from ..modules.discriminator import DiscriminatorP, DiscriminatorS
 from ..modules.rel_transformer import SinusoidalPositionalEmbedding
@@ -95,12 +97,23 @@ class VISinger(nn.Module):
             z_seg, ret["ids_slice"] = slice_segments(z_q, ids, self.segment_size), ids
         ret["wav_out"] = self.decoder(z_seg, g=spk).squeeze(1)
 
-    def _sample_and_decode(self, frame_mask, spk, mu_p, logs_p, noise, ret, mask_decoder=False):
+    def _sample_and_decode(self, frame_mask, spk, mu_p, logs_p, noise, ret, mask_decoder=False, seeds=None, takes=1, first_take=0,
+                           noise_scale=1.0):
         """synthesis side: reparameterised prior sample, flow inverse, full-length decode (visinger.py:105-110).
         mask_decoder (not in the reference, which synthesises one utterance at a time): decode a padded batch so that every
-        item's samples equal its standalone synthesis (Generator.forward x_mask)."""
-        eps = torch.randn_like(mu_p) if noise is None else noise
-        z_p = (mu_p + eps * torch.exp(logs_p)) * frame_mask
+        item's samples equal its standalone synthesis (Generator.forward x_mask).
+        seeds (not in the reference): one integer per item; the sample is drawn from the item's own counter-based stream in one launch
+        (sampling.prior_sample), `takes` of them per item -- the prior above ran once on B rows, the flow inverse and the generator run on
+        B * takes rows, item-major."""
+        if seeds is not None:
+            z_p = sampling.prior_sample(mu_p, logs_p, frame_mask, seeds, takes=takes, first_take=first_take, noise_scale=noise_scale)
+            if takes > 1:
+                frame_mask = frame_mask.repeat_interleave(takes, dim=0)
+                if torch.is_tensor(spk):
+                    spk = spk.repeat_interleave(takes, dim=0)
+        else:
+            eps = torch.randn_like(mu_p) if noise is None else noise
+            z_p = (mu_p + eps * torch.exp(logs_p)) * frame_mask
         z_q = self.flow(z_p, frame_mask, g=spk, reverse=True) * frame_mask
         if mask_decoder:
             ret["wav_out"] = self.decoder(z_q * frame_mask, g=spk, x_mask=frame_mask).squeeze(1)
@@ -108,11 +121,20 @@ class VISinger(nn.Module):
             ret["wav_out"] = self.decoder(z_q * frame_mask, g=spk).squeeze(1)
 
     def forward(self, text_tokens, pitch_tokens, dur_tokens, mel2ph, spk_embed=None, spk_id=None, f0=None, uv=None,
-                mel=None, infer=False, noise=None, noise_q=None, u_slice=None, mask_decoder=False, **kwargs):
+                mel=None, infer=False, noise=None, noise_q=None, u_slice=None, mask_decoder=False, seeds=None, takes=1, first_take=0,
+                noise_scale=1.0, **kwargs):
+        if seeds is not None:
+            if noise is not None:
+                raise ValueError("seeds and noise are two sources of the same sample: give one of them")
+            if not infer:
+                raise ValueError("seeds apply to the synthesis path only (infer=True)")
+        elif takes != 1 or first_take != 0 or noise_scale != 1.0:
+            raise ValueError("takes / first_take / noise_scale belong to the seeded path: give seeds")
         ret = {}
         frame_mask, spk, mu_p, logs_p = self._prior(text_tokens, pitch_tokens, dur_tokens, mel2ph, spk_embed, spk_id, f0, uv, ret)
         if infer:
-            self._sample_and_decode(frame_mask, spk, mu_p, logs_p, noise, ret, mask_decoder=mask_decoder)
+            self._sample_and_decode(frame_mask, spk, mu_p, logs_p, noise, ret, mask_decoder=mask_decoder, seeds=seeds, takes=takes,
+                                    first_take=first_take, noise_scale=noise_scale)
         else:
             self._posterior_branch(mel, frame_mask, spk, mu_p, logs_p, noise_q, u_slice, ret)
         return ret

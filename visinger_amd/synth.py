@@ -5,6 +5,8 @@ int16).  Host-side plumbing only."""
 import numpy as np
 import torch
 
+from . import sampling
+
 
 def bucket_by_length(lengths, max_frames_per_batch, max_items_per_batch=256, keys=None):
     """Sort by length (descending) and cut batches under a padded-frame budget (the reference's batch_by_size idea,
@@ -96,7 +98,10 @@ class GraphedStep:
     """One synthesis step (VISinger.forward(infer=True)) of a FIXED shape captured into a HIP graph and replayed: what a serving
     loop with recurring batch shapes does.  Every launch of the step goes to torch's current stream through the C ABI, nothing
     allocates with hipMalloc or synchronises with the host after the warm-up, so the ~700 launches of a step replay as one graph
-    (tests/test_model_gpu.py::test_synthesis_step_is_graph_capturable).  Inputs are copied into the graph's static buffers."""
+    (tests/test_model_gpu.py::test_synthesis_step_is_graph_capturable).  Inputs are copied into the graph's static buffers.
+    With seeds= (int64 CUDA tensor [B]; `noise` is then None) the step samples from the items' seeded streams (sampling.prior_sample), `takes` per item:
+    the kernel reads the seeds from a static device buffer, so a replay under other seeds is that buffer overwritten.  takes / first_take / noise_scale
+    are launch arguments: fixed by the capture."""
 
     @staticmethod
     def fingerprint(model):
@@ -104,15 +109,19 @@ class GraphedStep:
         through `.data`, like the packed-weight caches: call hipconv.repack_weights AND drop the graphs after such an edit)"""
         return tuple((p.data_ptr(), p._version) for p in model.parameters())
 
-    def __init__(self, model, batch, noise, mask_decoder):
+    def __init__(self, model, batch, noise, mask_decoder, seeds=None, takes=1, first_take=0, noise_scale=1.0):
+        if seeds is not None and noise is not None:
+            raise ValueError("seeds and noise are two sources of the same sample: give one of them")
         self.weights = self.fingerprint(model)       # a replay never re-folds / re-packs weights: the graph is only valid for these
         self.static = {k: v.clone() for k, v in batch.items()}
-        self.noise = noise.clone()
+        self.noise = None if seeds is not None else noise.clone()
+        self.seeds = None if seeds is None else sampling.seeds_tensor(seeds).clone()
+        sample = dict(noise=self.noise) if seeds is None else dict(seeds=self.seeds, takes=takes, first_take=first_take, noise_scale=noise_scale)
 
         def run():
             b = self.static
             return model(b["text_tokens"], b["pitch_tokens"], b["dur_tokens"], b["mel2ph"], spk_id=b["spk_id"], infer=True,
-                         noise=self.noise, mask_decoder=mask_decoder)["wav_out"]
+                         mask_decoder=mask_decoder, **sample)["wav_out"]
 
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
@@ -123,17 +132,22 @@ class GraphedStep:
         with torch.cuda.graph(self.graph):
             self.out = run()
 
-    def __call__(self, batch, noise):
+    def __call__(self, batch, noise, seeds=None):
+        if (self.seeds is None) != (seeds is None) or (self.noise is None) != (noise is None):
+            raise ValueError("a graph captured with noise is replayed with noise, one captured with seeds with seeds")
         for k, v in batch.items():
             self.static[k].copy_(v)
-        self.noise.copy_(noise)
+        if self.seeds is not None:
+            self.seeds.copy_(seeds)
+        else:
+            self.noise.copy_(noise)
         self.graph.replay()
         return self.out          # the graph's STATIC output buffer: the next replay overwrites it (clone to keep it)
 
 
 @torch.no_grad()
 def synthesize(model, items, hop_size, max_frames_per_batch=32768, noise_scale=1.0, generator=None, equal_tokens=False,
-               graphs=None, streams=2):
+               graphs=None, streams=2, seeds=None, takes=1, first_take=0):
     """Run VISinger.forward(infer=True) over length-bucketed batches.  Returns a list of float32 waveforms trimmed to
     each item's own length (frames * hop_size), in the input order.
 
@@ -153,7 +167,26 @@ def synthesize(model, items, hop_size, max_frames_per_batch=32768, noise_scale=1
 
     streams: consecutive batches go to alternating HIP streams (StreamRotation: the next batch's transformers run under this batch's generator); a batch's
     waveforms come back to the host when `streams` later batches have been issued.  The result is bit-identical to streams = 1 (same kernels, same inputs: the
-    noise of every batch is drawn on the caller's stream, in batch order).  With `graphs` the batches replay on the caller's stream (one stream)."""
+    noise of every batch is drawn on the caller's stream, in batch order).  With `graphs` the batches replay on the caller's stream (one stream).
+
+    seeds: one integer in [0, 2^63) per item, in input order, or a single integer s (item i gets (s + i) mod 2^63).  The prior sample of item i is then
+    drawn on the device from the item's own counter-based stream (sampling.prior_sample; noise_scale goes to the kernel) instead of the batch-wide
+    torch.randn: the waveform depends on (model, item, seed) only -- not on the bucket, the row, the padding or what was synthesised before.
+    takes > 1 (seeded path only): `takes` samples per item, take indices first_take .. first_take + takes - 1, from ONE pass of the text encoder, pitch
+    predictor and frame prior; entry i of the result is then a float32 array [takes, frames_i * hop_size].  The padded-frame and item budgets count
+    decoded rows: buckets are cut with max_frames_per_batch // takes and 256 // takes items."""
+    if seeds is not None:
+        if generator is not None:
+            raise ValueError("seeds and generator are two sources of the same noise: give one of them")
+        if isinstance(seeds, int) and not isinstance(seeds, bool):
+            sampling.check_seeds([seeds])
+            seeds = [(seeds + i) % sampling.SEED_LIMIT for i in range(len(items))]
+        seeds = sampling.check_seeds(seeds)
+        if len(seeds) != len(items):
+            raise ValueError(f"{len(seeds)} seeds for {len(items)} items")
+        takes, first_take = sampling.check_takes(takes, first_take)
+    elif takes != 1 or first_take != 0:
+        raise ValueError("takes / first_take select samples of the seeded streams: give seeds")
     device = next(model.parameters()).device
     lengths = [int((np.asarray(it["mel2ph"]) > 0).sum()) for it in items]
     out = [None] * len(items)
@@ -164,25 +197,34 @@ def synthesize(model, items, hop_size, max_frames_per_batch=32768, noise_scale=1
     def collect(idx, wav_dev, ev):
         if ev is not None:
             ev.synchronize()
-        wav = wav_dev.float().cpu().numpy()
+        wav = wav_dev.float().cpu().numpy()             # [B * takes, L], item-major
         for b, i in enumerate(idx):
-            out[i] = wav[b, :lengths[i] * hop_size].copy()
+            if takes == 1:
+                out[i] = wav[b, :lengths[i] * hop_size].copy()
+            else:
+                out[i] = wav[b * takes:(b + 1) * takes, :lengths[i] * hop_size].copy()
 
-    for idx in bucket_by_length(lengths, max_frames_per_batch, keys=keys):
+    for idx in bucket_by_length(lengths, max(1, max_frames_per_batch // takes), max_items_per_batch=max(1, 256 // takes), keys=keys):
         batch = collate([items[i] for i in idx], device)
         B, T = batch["mel2ph"].shape
-        noise = torch.randn((B, model.hidden_size, T), device=device, generator=generator) * noise_scale
         ragged = len({lengths[i] for i in idx}) > 1
+        if seeds is None:
+            noise, seeds_dev = torch.randn((B, model.hidden_size, T), device=device, generator=generator) * noise_scale, None
+            sample, key_tail = dict(noise=noise), ()
+        else:                                        # (the seeds travel with the batch; the kernel reads them on the device)
+            noise, seeds_dev = None, torch.tensor([seeds[i] for i in idx], dtype=torch.int64).to(device)
+            sample = dict(seeds=seeds_dev, takes=takes, first_take=first_take, noise_scale=noise_scale)
+            key_tail = ("seeded", takes, first_take, float(noise_scale))      # (launch arguments of the sampling kernel: fixed by a capture)
         if graphs is not None:
-            key = (B, batch["text_tokens"].shape[1], T, ragged)
+            key = (B, batch["text_tokens"].shape[1], T, ragged) + key_tail
             if key not in graphs or graphs[key].weights != GraphedStep.fingerprint(model):      # (re-captured after a weight update)
-                graphs[key] = GraphedStep(model, batch, noise, ragged)
-            collect(idx, graphs[key](batch, noise), None)
+                graphs[key] = GraphedStep(model, batch, noise, ragged, **{k: v for k, v in sample.items() if k != "noise"})
+            collect(idx, graphs[key](batch, noise, seeds=seeds_dev), None)
             continue
 
-        def run(batch=batch, noise=noise, ragged=ragged):
+        def run(batch=batch, sample=sample, ragged=ragged):
             return model(batch["text_tokens"], batch["pitch_tokens"], batch["dur_tokens"], batch["mel2ph"],
-                         spk_id=batch["spk_id"], infer=True, noise=noise, mask_decoder=ragged)["wav_out"]
+                         spk_id=batch["spk_id"], infer=True, mask_decoder=ragged, **sample)["wav_out"]
 
         if rotation is None:
             collect(idx, run(), None)
@@ -190,7 +232,7 @@ def synthesize(model, items, hop_size, max_frames_per_batch=32768, noise_scale=1
         for st in rotation.streams:              # (this batch's inputs were made on the caller's stream)
             st.wait_stream(torch.cuda.current_stream())
         wav_dev, ev = rotation.run(run)
-        for t in list(batch.values()) + [noise]:
+        for t in list(batch.values()) + [noise if seeds_dev is None else seeds_dev]:
             t.record_stream(rotation.streams[(rotation.count - 1) % len(rotation.streams)])      # (their memory is reused only behind that stream's work)
         pending.append((idx, wav_dev, ev))
         if len(pending) > len(rotation.streams):
