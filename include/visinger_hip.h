@@ -38,7 +38,7 @@ VS_API const char *vs_last_error(void);
  * this library, so a caller that attributes per-launch timings to kernel instances (bench.py's roofline line) reads it back
  * here instead of restating the selection.  Thread-local; "" before the first launch.  (No reference counterpart.)          */
 VS_API const char *vs_last_kernel_name(void);
-VS_API int vs_abi_version(void);          /* 7: vs_normal_fill, vs_prior_sample (appended to 7: new exports only, no layout or signature changed), vs_conv_set_weights_batch, vs_weight_norm_multi_fwd / _bwd, vs_conv_wgrad_bias, vs_wn_step_fwd / _bwd, vs_l1_mean_fwd / _bwd; 6: vs_source_hash, vs_bias_grad, vs_conv_set_weights_pair; 5: vs_relattn_fwd_work / vs_relattn_kv_work_bytes; 4: vs_set_option / vs_get_option / vs_reset_option; 3: vs_dtype in vs_conv_io_t; 2: vs_relattn_fwd(math) */
+VS_API int vs_abi_version(void);          /* 7: vs_f0_norm_interp, vs_pitch_condition, vs_normal_fill, vs_prior_sample (appended to 7: new exports only, no layout or signature changed),vs_conv_set_weights_batch, vs_weight_norm_multi_fwd / _bwd, vs_conv_wgrad_bias, vs_wn_step_fwd / _bwd, vs_l1_mean_fwd / _bwd; 6: vs_source_hash, vs_bias_grad, vs_conv_set_weights_pair; 5: vs_relattn_fwd_work / vs_relattn_kv_work_bytes; 4: vs_set_option / vs_get_option / vs_reset_option; 3: vs_dtype in vs_conv_io_t; 2: vs_relattn_fwd(math) */
 /* sha256 (hex) over the sources this library was compiled from (kernels, headers, textual includes, the build recipe), embedded by
  * visinger_amd/csrc/build.py.  The loader recomputes it over the tree it sits in and refuses a library built from other sources (a
  * stale object that an mtime check would pass after a checkout).  (No reference counterpart: the reference has no native code.)  */
@@ -348,6 +348,27 @@ VS_API int vs_normal_fill(const int64_t *seeds, int64_t take0, int64_t K, float 
 VS_API int vs_prior_sample(const float *mu, const float *logs, int64_t stat_batch_stride, const float *mask, const int64_t *seeds,
                            int64_t take0, int64_t K, float noise_scale, float *z, float *eps_out, int64_t B, int64_t H, int64_t T,
                            void *stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * f4  the pitch curve of synthesis (csrc/pitch_ops.hip): a guide curve in Hz, a transposition in cents, the sung curve back in Hz.
+ *     vs_f0_norm_interp: utils/audio/pitch/utils.py:42-57 (norm_interp_f0, one item at a time through numpy there) per row of f0_hz [B, T], on
+ *       the first lengths[b] frames (lengths: DEVICE int64 [B], clamped to [0, T]; NULL = T):  uv = 1 where f0_hz == 0, else 0;  f0_norm =
+ *       log2f(f0_hz + 1) on voiced frames, the straight line between the two voiced neighbours on an unvoiced frame between them, the first /
+ *       last voiced value before / after them (np.interp's edge rule), 0 on a row without a voiced frame.  Frames at or beyond lengths[b]:
+ *       f0_norm = 0, uv = 0 (the collate padding) -- they take no part in the interpolation.  A negative, NaN or infinite value counts as
+ *       unvoiced (uv = 1; the reference produces NaN there).  A row's result depends on its own frames only (not on B, the row, T).
+ *       One workgroup per row, a two-pass chunked scan; f0_norm doubles as the scan's scratch, so the three buffers must be distinct.
+ *     vs_pitch_condition: the frame prior's condition, models/visinger.py:129-135, plus the edits, per (b, t):
+ *       x = f0_norm[b, t] if given, else pred[b, t, 0];  voiced = (uv[b, t] == 0) if uv is given, else (pred[b, t, 1] <= 0);
+ *       if cents != NULL and cents[b] != 0:  x = log2f((exp2f(x) - 1) * exp2f(cents[b] / 1200) + 1)   (a zero shift leaves x's bits alone);
+ *       m = mask[b, t] (NULL: 1);  cond = (voiced && m != 0) ? x * m : 0;  f0_hz_out (optional) = clamp(exp2f(x) - 1, 50, 1250) on those
+ *       frames (denorm_f0's default range), 0 elsewhere.  pred: dense [B, T, 2], 8-byte aligned.  cents: DEVICE fp32 [B].
+ *     VS_EINVAL before anything is launched: NULL f0_hz / f0_norm / uv resp. cond, aliased buffers, B, T <= 0, T >= 2^24 (vs_f0_norm_interp:
+ *     frame distances are exact in fp32 below it), pred and f0_norm both NULL, uv and pred both NULL.  One launch each, no allocation, no atomics,
+ *     no host synchronisation: a captured graph replays with another curve / other shifts by overwriting the buffers.                  */
+VS_API int vs_f0_norm_interp(const float *f0_hz, const int64_t *lengths, float *f0_norm, float *uv, int64_t B, int64_t T, void *stream);
+VS_API int vs_pitch_condition(const float *pred, const float *f0_norm, const float *uv, const float *mask, const float *cents, float *cond,
+                              float *f0_hz_out, int64_t B, int64_t T, void *stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * a13 grouped / strided Conv1d of the scale discriminator (modules/discriminator.py:55-60) and its gradients.

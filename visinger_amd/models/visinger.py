@@ -11,13 +11,17 @@ reference (and is parity-tested against its golden output).
 RNG: ``noise`` / ``noise_q`` / ``u_slice`` may be injected for reproducible parity (CPU and GPU generators differ);
 when omitted they are drawn exactly where the reference draws them.  ``seeds`` (synthesis only) draws the prior sample from per-item
 counter-based streams on the device instead (visinger_amd/sampling.py): an item's waveform then depends on (weights, item, seed) alone.
+
+Pitch control (not in the reference; visinger_amd/pitch.py): ``f0_hz`` is a guide curve in Hz per frame (0 = unvoiced), normalised
+and gap-interpolated on the device; ``voicing`` takes the voiced frames from the guide or from the predictor; ``pitch_shift_cents`` transposes
+the conditioning curve per item; ``ret["f0_hz"]`` is then the curve the prior was conditioned on, in Hz.
 """
 from copy import deepcopy
 
 import torch
 import torch.nn as nn
 
-from .. import sampling
+from .. import pitch, sampling
 from ..modules.commons.utils import Embedding, rand_slice_segments, slice_segments
 from ..modules.discriminator import DiscriminatorP, DiscriminatorS
 from ..modules.rel_transformer import SinusoidalPositionalEmbedding
@@ -67,7 +71,7 @@ class VISinger(nn.Module):
                                  hp["initial_upsample_channels"], hp["upsample_kernel_sizes"], gin_channels=gin)
 
     # ---- pieces of forward ----------------------------------------------------------------------------------------------
-    def _prior(self, text_tokens, pitch_tokens, dur_tokens, mel2ph, spk_embed, spk_id, f0, uv, ret):
+    def _prior(self, text_tokens, pitch_tokens, dur_tokens, mel2ph, spk_embed, spk_id, f0, uv, ret, pitch_edit=None):
         """frame mask, speaker condition and the prior's (mu_p, logs_p): visinger.py:73-90"""
         frame_mask = (mel2ph > 0).float().unsqueeze(1)                                     # [B, 1, T]
         h = self.text_encoder(text_tokens, pitch_tokens, dur_tokens, mel2ph) * frame_mask  # [B, H, T]
@@ -78,7 +82,10 @@ class VISinger(nn.Module):
         cond = None
         if self.hparams["use_pitch_embed"]:
             # [B, 1, T] -> [B, T, 1]: FramePriorNetwork transposes its condition back (see the module docstring)
-            cond = self.forward_pitch(h, f0, uv, spk, frame_mask, ret).transpose(1, 2)
+            if pitch_edit is None:
+                cond = self.forward_pitch(h, f0, uv, spk, frame_mask, ret).transpose(1, 2)
+            else:
+                cond = self.forward_pitch_edit(h, f0, uv, spk, frame_mask, mel2ph, ret, *pitch_edit).transpose(1, 2)
         mu_p, logs_p = self.frame_prior(h, frame_mask, cond)
         return frame_mask, spk, mu_p, logs_p
 
@@ -122,7 +129,16 @@ class VISinger(nn.Module):
 
     def forward(self, text_tokens, pitch_tokens, dur_tokens, mel2ph, spk_embed=None, spk_id=None, f0=None, uv=None,
                 mel=None, infer=False, noise=None, noise_q=None, u_slice=None, mask_decoder=False, seeds=None, takes=1, first_take=0,
-                noise_scale=1.0, **kwargs):
+                noise_scale=1.0, f0_hz=None, voicing="guide", pitch_shift_cents=None, **kwargs):
+        if voicing not in ("guide", "model"):
+            raise ValueError(f"voicing must be 'guide' or 'model', got {voicing!r}")
+        pitch_edit = None
+        if f0_hz is not None or pitch_shift_cents is not None or voicing != "guide":
+            if f0_hz is not None and (f0 is not None or uv is not None):
+                raise ValueError("f0_hz (a guide in Hz) and f0 / uv (a normalised curve) are two sources of the same curve: give one of them")
+            if not self.hparams["use_pitch_embed"]:
+                raise ValueError("f0_hz / voicing / pitch_shift_cents need a model with use_pitch_embed: this one has no pitch condition")
+            pitch_edit = (f0_hz, voicing, pitch_shift_cents)
         if seeds is not None:
             if noise is not None:
                 raise ValueError("seeds and noise are two sources of the same sample: give one of them")
@@ -131,7 +147,7 @@ class VISinger(nn.Module):
         elif takes != 1 or first_take != 0 or noise_scale != 1.0:
             raise ValueError("takes / first_take / noise_scale belong to the seeded path: give seeds")
         ret = {}
-        frame_mask, spk, mu_p, logs_p = self._prior(text_tokens, pitch_tokens, dur_tokens, mel2ph, spk_embed, spk_id, f0, uv, ret)
+        frame_mask, spk, mu_p, logs_p = self._prior(text_tokens, pitch_tokens, dur_tokens, mel2ph, spk_embed, spk_id, f0, uv, ret, pitch_edit)
         if infer:
             self._sample_and_decode(frame_mask, spk, mu_p, logs_p, noise, ret, mask_decoder=mask_decoder, seeds=seeds, takes=takes,
                                     first_take=first_take, noise_scale=noise_scale)
@@ -161,6 +177,27 @@ class VISinger(nn.Module):
         else:
             voiced = uv == 0
         return (f0 * voiced).unsqueeze(1) * tgt_nonpadding
+
+    def forward_pitch_edit(self, pitch_inp, f0, uv, spk_emb, tgt_nonpadding, mel2ph, ret, f0_hz, voicing, cents):
+        """forward_pitch under pitch control: the predictor runs as always (ret["f0_pred"]); the condition comes from one launch
+        (pitch.pitch_condition) on the guide curve f0_hz (Hz, 0 = unvoiced; normalised and gap-interpolated on the device over each item's
+        own frames, pitch.norm_interp_f0), on the teacher-forced f0 / uv, or on the predicted curve -- transposed by `cents` per item.
+        voicing="guide": voiced where the guide is (equal to the reference's forward(f0=, uv=) on its own norm_interp_f0 of the item);
+        "model": the interpolated guide under the predictor's voicing.  ret["f0_hz"]: the curve that conditions the prior, in Hz."""
+        scale = self.hparams["predictor_grad"]
+        if scale != 1:
+            stopped = pitch_inp.detach()
+            pitch_inp = stopped + scale * (pitch_inp - stopped)
+        pred = ret["f0_pred"] = self.pitch_predictor(pitch_inp, tgt_nonpadding, spk_emb)      # [B, T, 2]
+        if f0_hz is not None:
+            lengths = (mel2ph > 0).sum(dim=1)                                                  # int64 [B], stays on the device
+            f0, uv = pitch.norm_interp_f0(f0_hz, lengths)
+            if voicing == "model":
+                uv = None
+        # (the voicing decision carries no gradient, and a given curve is data: only a SHIFTED PREDICTED curve would need a backward)
+        src = None if (f0 is not None and uv is not None) else (pred.detach() if f0 is not None else pred)
+        cond, ret["f0_hz"] = pitch.pitch_condition(tgt_nonpadding, pred=src, f0_norm=f0, uv=uv, cents=cents, return_hz=True)
+        return cond.to(tgt_nonpadding.dtype)
 
 
 class MultiPeriodDiscriminator(nn.Module):

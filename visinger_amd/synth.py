@@ -5,7 +5,7 @@ int16).  Host-side plumbing only."""
 import numpy as np
 import torch
 
-from . import sampling
+from . import pitch, sampling
 
 
 def bucket_by_length(lengths, max_frames_per_batch, max_items_per_batch=256, keys=None):
@@ -27,7 +27,12 @@ def bucket_by_length(lengths, max_frames_per_batch, max_items_per_batch=256, key
 
 
 def collate(items, device):
-    """items: dicts with int64 1-D arrays text_tokens, pitch_tokens, dur_tokens (T_ph) and mel2ph (T_mel); 0-padded."""
+    """items: dicts with int64 1-D arrays text_tokens, pitch_tokens, dur_tokens (T_ph) and mel2ph (T_mel); 0-padded.
+    An item may carry "f0": a guide curve in Hz, one value per frame of its mel2ph (0 = unvoiced) -> batch["f0_hz"], fp32 [B, T_mel], padded
+    with 0.  Either every item of a batch has one or none (synthesize keeps them apart); a length mismatch is a ValueError."""
+    guided = ["f0" in it and it["f0"] is not None for it in items]
+    if any(guided) and not all(guided):
+        raise ValueError("items with and without a guide curve ('f0') cannot share a batch")
     Tph = max(len(it["text_tokens"]) for it in items)
     T = max(len(it["mel2ph"]) for it in items)
     out = {k: torch.zeros((len(items), Tph if k != "mel2ph" else T), dtype=torch.long)
@@ -37,6 +42,13 @@ def collate(items, device):
             v = torch.as_tensor(np.asarray(it[k]), dtype=torch.long)
             out[k][b, :len(v)] = v
     out["spk_id"] = torch.as_tensor([int(it.get("spk_id", 0)) for it in items], dtype=torch.long)
+    if guided and guided[0]:
+        out["f0_hz"] = torch.zeros((len(items), T), dtype=torch.float32)
+        for b, it in enumerate(items):
+            v = torch.as_tensor(np.asarray(it["f0"], dtype=np.float32))
+            if v.dim() != 1 or len(v) != len(it["mel2ph"]):
+                raise ValueError(f"item {b}: the guide curve has {tuple(v.shape)} values for {len(it['mel2ph'])} frames (one value in Hz per frame)")
+            out["f0_hz"][b, :len(v)] = v
     return {k: v.to(device) for k, v in out.items()}
 
 
@@ -101,7 +113,10 @@ class GraphedStep:
     (tests/test_model_gpu.py::test_synthesis_step_is_graph_capturable).  Inputs are copied into the graph's static buffers.
     With seeds= (int64 CUDA tensor [B]; `noise` is then None) the step samples from the items' seeded streams (sampling.prior_sample), `takes` per item:
     the kernel reads the seeds from a static device buffer, so a replay under other seeds is that buffer overwritten.  takes / first_take / noise_scale
-    are launch arguments: fixed by the capture."""
+    are launch arguments: fixed by the capture.
+    Pitch control: a batch with "f0_hz" (collate) is synthesised on that guide curve -- it sits among the static inputs like the tokens, so a replay under
+    another curve is that buffer overwritten; cents= (anything pitch.cents_tensor takes) becomes a static fp32 [B] buffer the kernel reads, overwritten by
+    __call__(cents=).  `voicing` is fixed by the capture.  With either, `f0_hz_out` is the static [B, T] buffer of the sung curve in Hz."""
 
     @staticmethod
     def fingerprint(model):
@@ -109,7 +124,7 @@ class GraphedStep:
         through `.data`, like the packed-weight caches: call hipconv.repack_weights AND drop the graphs after such an edit)"""
         return tuple((p.data_ptr(), p._version) for p in model.parameters())
 
-    def __init__(self, model, batch, noise, mask_decoder, seeds=None, takes=1, first_take=0, noise_scale=1.0):
+    def __init__(self, model, batch, noise, mask_decoder, seeds=None, takes=1, first_take=0, noise_scale=1.0, voicing="guide", cents=None):
         if seeds is not None and noise is not None:
             raise ValueError("seeds and noise are two sources of the same sample: give one of them")
         self.weights = self.fingerprint(model)       # a replay never re-folds / re-packs weights: the graph is only valid for these
@@ -117,11 +132,17 @@ class GraphedStep:
         self.noise = None if seeds is not None else noise.clone()
         self.seeds = None if seeds is None else sampling.seeds_tensor(seeds).clone()
         sample = dict(noise=self.noise) if seeds is None else dict(seeds=self.seeds, takes=takes, first_take=first_take, noise_scale=noise_scale)
+        self.cents = None if cents is None else pitch.cents_tensor(cents, batch["mel2ph"].shape[0], batch["mel2ph"].device).clone()
+        self.f0_hz_out = None
+        if "f0_hz" in batch or self.cents is not None:
+            sample.update(f0_hz=self.static.get("f0_hz"), voicing=voicing, pitch_shift_cents=self.cents)
 
         def run():
             b = self.static
-            return model(b["text_tokens"], b["pitch_tokens"], b["dur_tokens"], b["mel2ph"], spk_id=b["spk_id"], infer=True,
-                         mask_decoder=mask_decoder, **sample)["wav_out"]
+            ret = model(b["text_tokens"], b["pitch_tokens"], b["dur_tokens"], b["mel2ph"], spk_id=b["spk_id"], infer=True,
+                        mask_decoder=mask_decoder, **sample)
+            self.f0_hz_out = ret.get("f0_hz")
+            return ret["wav_out"]
 
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
@@ -132,11 +153,15 @@ class GraphedStep:
         with torch.cuda.graph(self.graph):
             self.out = run()
 
-    def __call__(self, batch, noise, seeds=None):
+    def __call__(self, batch, noise, seeds=None, cents=None):
         if (self.seeds is None) != (seeds is None) or (self.noise is None) != (noise is None):
             raise ValueError("a graph captured with noise is replayed with noise, one captured with seeds with seeds")
+        if ("f0_hz" in batch) != ("f0_hz" in self.static) or (self.cents is None) != (cents is None):
+            raise ValueError("a graph is replayed with the inputs it was captured with (guide curve and pitch shift included)")
         for k, v in batch.items():
             self.static[k].copy_(v)
+        if self.cents is not None:
+            self.cents.copy_(pitch.cents_tensor(cents, self.cents.shape[0], self.cents.device))
         if self.seeds is not None:
             self.seeds.copy_(seeds)
         else:
@@ -147,7 +172,7 @@ class GraphedStep:
 
 @torch.no_grad()
 def synthesize(model, items, hop_size, max_frames_per_batch=32768, noise_scale=1.0, generator=None, equal_tokens=False,
-               graphs=None, streams=2, seeds=None, takes=1, first_take=0):
+               graphs=None, streams=2, seeds=None, takes=1, first_take=0, voicing="guide", pitch_shift_cents=None, return_f0=False):
     """Run VISinger.forward(infer=True) over length-bucketed batches.  Returns a list of float32 waveforms trimmed to
     each item's own length (frames * hop_size), in the input order.
 
@@ -174,7 +199,17 @@ def synthesize(model, items, hop_size, max_frames_per_batch=32768, noise_scale=1
     torch.randn: the waveform depends on (model, item, seed) only -- not on the bucket, the row, the padding or what was synthesised before.
     takes > 1 (seeded path only): `takes` samples per item, take indices first_take .. first_take + takes - 1, from ONE pass of the text encoder, pitch
     predictor and frame prior; entry i of the result is then a float32 array [takes, frames_i * hop_size].  The padded-frame and item budgets count
-    decoded rows: buckets are cut with max_frames_per_batch // takes and 256 // takes items."""
+    decoded rows: buckets are cut with max_frames_per_batch // takes and 256 // takes items.
+
+    Pitch control (VISinger.forward f0_hz / voicing / pitch_shift_cents; needs use_pitch_embed): an item with "f0" -- a curve in Hz, one value per frame of
+    its mel2ph, 0 = unvoiced -- is sung on that guide; voicing="guide" takes the voiced frames from it, "model" keeps the predictor's own decision over the
+    gap-interpolated guide.  Items with and without a guide never share a batch.  pitch_shift_cents: a number, or one per item in input order; transposes the
+    conditioning curve (guide or predicted), read on the device.  return_f0: the result is a list of (wav, f0_hz) with f0_hz the float32 curve the prior was
+    conditioned on, in Hz (0 = unvoiced), trimmed to the item's frames.  Items without "f0" in a call without these arguments run exactly as before."""
+    if voicing not in ("guide", "model"):
+        raise ValueError(f"voicing must be 'guide' or 'model', got {voicing!r}")
+    if pitch_shift_cents is not None:
+        pitch_shift_cents = pitch.cents_tensor(pitch_shift_cents, len(items), "cpu").tolist()      # (checked here; a batch's values travel with the batch)
     if seeds is not None:
         if generator is not None:
             raise ValueError("seeds and generator are two sources of the same noise: give one of them")
@@ -190,19 +225,28 @@ def synthesize(model, items, hop_size, max_frames_per_batch=32768, noise_scale=1
     device = next(model.parameters()).device
     lengths = [int((np.asarray(it["mel2ph"]) > 0).sum()) for it in items]
     out = [None] * len(items)
+    guided = ["f0" in it and it["f0"] is not None for it in items]
+    for i, it in enumerate(items):
+        if guided[i] and np.shape(it["f0"]) != (len(it["mel2ph"]),):
+            raise ValueError(f"item {i}: the guide curve has {np.shape(it['f0'])} values for {len(it['mel2ph'])} frames (one value in Hz per frame)")
     keys = [len(it["text_tokens"]) for it in items] if equal_tokens else None
+    if any(guided):
+        keys = [(g, k) for g, k in zip(guided, keys if keys is not None else [0] * len(items))]
     rotation = StreamRotation(streams) if (graphs is None and streams and streams > 1) else None
     pending = []                                 # (item indices, device waveforms, event) of the batches in flight
 
-    def collect(idx, wav_dev, ev):
+    def collect(idx, wav_dev, ev, f0_dev=None):
         if ev is not None:
             ev.synchronize()
         wav = wav_dev.float().cpu().numpy()             # [B * takes, L], item-major
+        f0 = f0_dev.float().cpu().numpy() if return_f0 else None      # [B, T]: the prior ran once per item
         for b, i in enumerate(idx):
             if takes == 1:
                 out[i] = wav[b, :lengths[i] * hop_size].copy()
             else:
                 out[i] = wav[b * takes:(b + 1) * takes, :lengths[i] * hop_size].copy()
+            if return_f0:
+                out[i] = (out[i], f0[b, :lengths[i]].copy())
 
     for idx in bucket_by_length(lengths, max(1, max_frames_per_batch // takes), max_items_per_batch=max(1, 256 // takes), keys=keys):
         batch = collate([items[i] for i in idx], device)
@@ -215,26 +259,35 @@ def synthesize(model, items, hop_size, max_frames_per_batch=32768, noise_scale=1
             noise, seeds_dev = None, torch.tensor([seeds[i] for i in idx], dtype=torch.int64).to(device)
             sample = dict(seeds=seeds_dev, takes=takes, first_take=first_take, noise_scale=noise_scale)
             key_tail = ("seeded", takes, first_take, float(noise_scale))      # (launch arguments of the sampling kernel: fixed by a capture)
+        # pitch control: a guided batch, a shift, or the curve asked back (a zero shift leaves the curve's bits alone and makes the model report it)
+        cents_dev, pitch_kw = None, {}
+        if "f0_hz" in batch or pitch_shift_cents is not None or return_f0:
+            cents_dev = pitch.cents_tensor([pitch_shift_cents[i] for i in idx] if pitch_shift_cents is not None else 0.0, B, device)
+            pitch_kw = dict(f0_hz=batch.get("f0_hz"), voicing=voicing, pitch_shift_cents=cents_dev)
         if graphs is not None:
-            key = (B, batch["text_tokens"].shape[1], T, ragged) + key_tail
+            key = (B, batch["text_tokens"].shape[1], T, ragged) + key_tail + ("f0_hz" in batch, voicing, cents_dev is not None)
             if key not in graphs or graphs[key].weights != GraphedStep.fingerprint(model):      # (re-captured after a weight update)
-                graphs[key] = GraphedStep(model, batch, noise, ragged, **{k: v for k, v in sample.items() if k != "noise"})
-            collect(idx, graphs[key](batch, noise, seeds=seeds_dev), None)
+                graphs[key] = GraphedStep(model, batch, noise, ragged, voicing=voicing, cents=cents_dev,
+                                          **{k: v for k, v in sample.items() if k != "noise"})
+            wav_dev = graphs[key](batch, noise, seeds=seeds_dev, cents=cents_dev)
+            collect(idx, wav_dev, None, graphs[key].f0_hz_out)
             continue
 
-        def run(batch=batch, sample=sample, ragged=ragged):
-            return model(batch["text_tokens"], batch["pitch_tokens"], batch["dur_tokens"], batch["mel2ph"],
-                         spk_id=batch["spk_id"], infer=True, mask_decoder=ragged, **sample)["wav_out"]
+        def run(batch=batch, sample=sample, ragged=ragged, pitch_kw=pitch_kw):
+            ret = model(batch["text_tokens"], batch["pitch_tokens"], batch["dur_tokens"], batch["mel2ph"],
+                        spk_id=batch["spk_id"], infer=True, mask_decoder=ragged, **sample, **pitch_kw)
+            return ret["wav_out"], ret.get("f0_hz")
 
         if rotation is None:
-            collect(idx, run(), None)
+            wav_dev, f0_dev = run()
+            collect(idx, wav_dev, None, f0_dev)
             continue
         for st in rotation.streams:              # (this batch's inputs were made on the caller's stream)
             st.wait_stream(torch.cuda.current_stream())
-        wav_dev, ev = rotation.run(run)
-        for t in list(batch.values()) + [noise if seeds_dev is None else seeds_dev]:
+        (wav_dev, f0_dev), ev = rotation.run(run)
+        for t in list(batch.values()) + [noise if seeds_dev is None else seeds_dev] + ([] if cents_dev is None else [cents_dev]):
             t.record_stream(rotation.streams[(rotation.count - 1) % len(rotation.streams)])      # (their memory is reused only behind that stream's work)
-        pending.append((idx, wav_dev, ev))
+        pending.append((idx, wav_dev, ev, f0_dev))
         if len(pending) > len(rotation.streams):
             collect(*pending.pop(0))
     for job in pending:
