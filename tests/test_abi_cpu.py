@@ -194,38 +194,54 @@ def test_conv_handles_survive_copy_and_pickle():
     import torch
     from visinger_amd import _lib as L
     from visinger_amd.modules.hipconv import HipConv1d, repack_weights
-    from visinger_amd.ops import ConvOp
+    from visinger_amd.ops import ConvOp, handles
     op = ConvOp(L.CONV1D, 8, 16, 3, 1, 1)
     op._pending_math = L.MATH_F32
     for clone in (copy.deepcopy(op), pickle.loads(pickle.dumps(op))):
         assert clone is not op and clone._args() == op._args() and clone._h is None and clone._pending_math == L.MATH_F32
         assert clone._wkey is None                                   # a copy re-binds its owner's parameters on first use
+    # every handle of a holder sits in its table (ops.handles), and the table copies and pickles EMPTY: the one place the rule lives
     m = HipConv1d(8, 16, 3, padding=1)
-    m.__dict__["_hip_ops"] = {(0, 0): op}
-    m.__dict__["_hip_bwd_ops"] = {"dx": ConvOp(L.CONV1D, 16, 8, 3, 1, 1)}
-    m2 = pickle.loads(pickle.dumps(m))
-    assert not any(k in m2.__dict__ for k in ("_hip_ops", "_hip_bwd_ops", "_hip_disc_ops"))
-    assert torch.equal(m2.weight, m.weight)
+    m.__dict__["_hip_math"] = L.MATH_F32                               # a setting, not a handle: travels with the module
+    assert handles(m).op(("fwd", L.CONV1D, 0), L.CONV1D, 8, 16, 3, 1, 1)._args() == op._args()
+    handles(m)[("fwd", L.CONV1D, 0)] = op
+    assert handles(m).get(("fwd", L.CONV1D, 0)) is op and handles(m).get("dxa") is None and "dxa" not in handles(m)      # (a look-up creates nothing)
+    dx = handles(m).op("dx", L.CONV1D, 16, 8, 3, 1, 1)
+    assert handles(m).op("dx", L.CONV1D, 16, 8, 3, 1, 1) is dx
+    for m2 in (pickle.loads(pickle.dumps(m)), copy.deepcopy(m)):
+        assert len(handles(m2)) == 0 and handles(m2) is not handles(m)
+        assert not any(isinstance(v, ConvOp) for v in m2.__dict__.values())
+        assert torch.equal(m2.weight, m.weight) and m2.weight is not m.weight
+        assert m2.__dict__["_hip_math"] == L.MATH_F32
+    assert len(handles(m)) == 2                                       # (the original keeps its own)
     plain = torch.nn.Conv1d(4, 4, 3)                                  # the discriminators' holders are stock nn.Conv1d / nn.Conv2d
-    plain.__dict__["_hip_disc_ops"] = {"fwd": op}
+    handles(plain)[("disc_fwd", 4, 4, 3, 1)] = op
     p2 = copy.deepcopy(plain)
-    assert p2.__dict__["_hip_disc_ops"]["fwd"] is not op and p2.__dict__["_hip_disc_ops"]["fwd"]._h is None
+    mine = list(handles(p2).values()) + [v for v in p2.__dict__.values() if isinstance(v, ConvOp)]
+    assert all(o is not op and o._h is None for o in mine) and handles(p2) is not handles(plain)
     op._wkey = ("stale",)
+    dx._wkey = ("stale",)
     repack_weights(m)
-    assert op._wkey is None
-    # the fused q | k | v projection of an attention layer is keyed on (data_ptr, _version) of six parameters, which a
-    # `.data` edit does not change: repack_weights must drop it (and its training twin), and it must never be pickled
+    assert op._wkey is None and dx._wkey is None
+    # the fused q | k | v projection of an attention layer is keyed on the parameters of three convs, which a `.data` edit does not
+    # change: repack_weights must reach it (forward handle and training twin), and it must never be pickled
     from visinger_amd.modules.rel_transformer import MultiHeadAttention, RelativeEncoder
     enc = RelativeEncoder(16, 32, 2, 1, kernel_size=3)
     att = enc.attn_layers[0]
-    att.__dict__["_hip_qkv_inf"] = op
-    att.__dict__["_hip_qkv"] = object()
+    qkv = att.fused_qkv()
+    assert qkv is att.fused_qkv() and handles(qkv) is handles(att)     # one holder per layer, its handles in the attention module's table
+    handles(att)[("fwd", L.CONV1D, 0)] = op
+    adj = handles(att).op("dxa", L.CONV1D, 48, 16, 1, 1, 0, L.CONV_ADJOINT)
     att.conv_q.weight.data.mul_(2.0)                                 # the edit the cache key cannot see
-    a2 = pickle.loads(pickle.dumps(att))
-    assert isinstance(a2, MultiHeadAttention) and not any(k in a2.__dict__ for k in ("_hip_qkv_inf", "_hip_qkv"))
-    assert torch.equal(a2.conv_q.weight, att.conv_q.weight)
+    for a2 in (pickle.loads(pickle.dumps(att)), copy.deepcopy(att)):
+        assert isinstance(a2, MultiHeadAttention) and len(handles(a2)) == 0 and handles(a2) is not handles(att)
+        assert not any(isinstance(v, ConvOp) for v in a2.__dict__.values())
+        assert torch.equal(a2.conv_q.weight, att.conv_q.weight)
+        q2 = a2.fused_qkv()                                          # the copy's holder serves the COPY: its convs, its table
+        assert q2 is not qkv and handles(q2) is handles(a2) and q2._key_sources == (a2.conv_q, a2.conv_k, a2.conv_v)
+    op._wkey = adj._wkey = ("stale",)
     repack_weights(enc)
-    assert not any(k in att.__dict__ for k in ("_hip_qkv_inf", "_hip_qkv"))
+    assert op._wkey is None and adj._wkey is None
 
 
 def test_dispatch_switches_are_read_once_and_set_through_the_abi():

@@ -454,8 +454,82 @@ def test_training_transformer_layer_uses_the_streaming_attention(vs_option):
             assert float((a - b).abs().max()) <= 1e-4 * float(b.abs().max()) + 1e-6
 
 
+def test_fused_qkv_projection_is_one_handle_for_inference_and_training():
+    """The q | k | v projection of an attention layer is ONE handle in the layer's table (ops.handles), shared by the fused inference path and the
+    training path and keyed by ops.param_key over the three convs: packed once per version of their parameters whichever mode asks first, re-packed
+    after bump_weight_epoch() / repack_weights() (edits through `.data`), and moved between arithmetics by set_math alone (no pack), with the bits
+    of a fresh pack in that arithmetic."""
+    from visinger_amd import _lib as L
+    from visinger_amd import ops
+    from visinger_amd.modules.hipconv import repack_weights, set_conv_math
+    from visinger_amd.modules.rel_transformer import RelativeEncoder
+
+    def build():
+        return RelativeEncoder(64, 128, 2, 1, kernel_size=3, p_dropout=0.0, window_size=4).cuda()
+
+    torch.manual_seed(11)
+    enc = build()
+    att = enc.attn_layers[0]
+    x = torch.randn(2, 64, 40).cuda()
+    mask = torch.ones(2, 1, 40).cuda()
+    mask[1, :, 27:] = 0
+
+    def infer(m):
+        m.eval()
+        with torch.no_grad():
+            return m(x, mask)
+
+    def qkv_op():
+        return ops.handles(att).get(("fwd", L.CONV1D, 0))
+
+    packed, orig = [], ops.ConvOp._pack
+
+    def counting(self, *args):
+        packed.append(self)
+        return orig(self, *args)
+
+    def packs():
+        return sum(o is qkv_op() for o in packed)
+
+    ops.ConvOp._pack = counting
+    try:
+        y0 = infer(enc)
+        op = qkv_op()
+        assert op is not None and (op.c_in, op.c_out, op.k) == (64, 192, 1) and packs() == 1
+        enc.train()
+        yt = enc(x.clone().requires_grad_(True), mask)
+        yt.sum().backward()
+        assert att.conv_q.weight.grad is not None and ops.handles(att).get("dxa") is not None      # (its grad-input twin, in the same table)
+        y1 = infer(enc)
+        assert qkv_op() is op and packs() == 1
+        assert torch.equal(y1, y0)
+        d = float((yt.detach() - y0).abs().max())
+        print("train vs eval forward: max |d| =", d, "of", float(y0.abs().max()))
+        assert d <= 2e-5 * max(1.0, float(y0.abs().max())), d              # (the bound of test_train_forward_equals_eval_forward)
+        # another arithmetic and back: set_math re-packs from the fp32 fragments the handle keeps
+        set_conv_math(enc, L.MATH_F32)
+        yf = infer(enc)
+        assert qkv_op() is op and op.math == L.MATH_F32
+        set_conv_math(enc, None)
+        y2 = infer(enc)
+        assert packs() == 1 and torch.equal(y2, y0)
+        fresh = build()
+        fresh.load_state_dict(enc.state_dict())
+        assert torch.equal(infer(set_conv_math(fresh, L.MATH_F32)), yf)
+        # an edit the parameter versions cannot see
+        att.conv_q.weight.data.mul_(1.5)
+        ops.bump_weight_epoch()
+        y3 = infer(enc)
+        assert qkv_op() is op and packs() == 2 and not torch.equal(y3, y0)
+        repack_weights(enc)
+        y4 = infer(enc)
+        assert packs() == 3 and torch.equal(y4, y3)
+    finally:
+        ops.ConvOp._pack = orig
+
+
 def test_training_step_packs_each_weight_version_once(vs_option):
-    """ConvOp.bind / autograd.param_key: within one optimizer step the discriminators' convs see their (unchanged)
+    """ConvOp.bind / ops.param_key: within one optimizer step the discriminators' convs see their (unchanged)
     parameters three times (real + generated batch in the generator pass, both in the discriminator pass) and every handle packs them
     once; after an optimizer step the versions differ and they are packed again.  The cached and the uncached run produce the SAME
     losses and parameters bit for bit (the packed bytes are identical), at fewer packs."""

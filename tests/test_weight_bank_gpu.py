@@ -112,7 +112,7 @@ def test_training_step_with_bank_equals_step_without(vs_option):
         batch["u_slice"] = torch.rand(2, generator=g).cuda()
         logs = tr.training_step(batch)
         # gradients of the second step's generator pass, before the optimizer consumes them
-        from visinger_amd.autograd import bump_weight_epoch
+        from visinger_amd.ops import bump_weight_epoch
         bump_weight_epoch()
         tr.backward_pass(batch, 0)
         grads = {n: p.grad.detach().clone() for n, p in tr.model.named_parameters() if p.grad is not None}

@@ -17,43 +17,9 @@ import torch
 import torch.nn.functional as F
 
 from . import _lib as L
-from .ops import PROFILER, ConvOp, bias_grad, conv_wgrad, gconv1d_bwd_data, gconv1d_bwd_weight, gconv1d_fwd
+from .ops import PROFILER, bias_grad, conv_wgrad, gconv1d_bwd_data, gconv1d_bwd_weight, gconv1d_fwd, handles, param_key
 
 LRELU_SLOPE = 0.1
-
-
-_WEIGHT_EPOCH = [0]
-
-
-def bump_weight_epoch():
-    """Invalidate every packed-weight key at once (the epoch is part of each key).  (data_ptr, _version) follows optimizer steps,
-    load_state_dict and copy_ on the parameter, but NOT edits made through ``p.data`` (EMA swaps, ``p.data.clamp_``: `.data` carries
-    its own version counter).  VISingerTrainer.training_step bumps the epoch once per step, so such an edit between two steps costs one
-    re-pack instead of silently training on stale packed weights; inside a step the cache still serves the frozen network's second use."""
-    _WEIGHT_EPOCH[0] += 1
-
-
-def param_key(holder):
-    """Identity and in-place versions of the PARAMETERS the live weight / bias of a conv holder derive from: (weight_v, weight_g) under
-    torch.nn.utils.weight_norm, else the plain weight parameter; None when the weight is not a function of parameters alone (spectral
-    norm runs a power iteration per forward).  Optimizer steps, load_state_dict and every other in-place write bump the versions; a
-    handle whose packed weights carry the same key need not be packed again (ConvOp.bind)."""
-    if L.switch("VS_NO_PACK_CACHE"):
-        return None
-    sources = holder.__dict__.get("_key_sources")
-    if sources is not None:                   # a fused projection (_ConvHolder): the concatenation of several modules' weights
-        keys = tuple(param_key(m_) for m_ in sources)
-        return None if any(k is None for k in keys) else keys
-    if not isinstance(holder, torch.nn.Module):
-        return None
-    if hasattr(holder, "weight_g") and hasattr(holder, "weight_v"):
-        ps = (holder.weight_v, holder.weight_g)
-    elif isinstance(holder._parameters.get("weight"), torch.nn.Parameter):
-        ps = (holder.weight,)
-    else:
-        return None
-    bias = getattr(holder, "bias", None)
-    return tuple((t.data_ptr(), t._version) for t in ps) + (None if bias is None else (bias.data_ptr(), bias._version), _WEIGHT_EPOCH[0])
 
 
 class HipConvFn(torch.autograd.Function):
@@ -66,7 +32,7 @@ class HipConvFn(torch.autograd.Function):
         x = x.contiguous().float()
         op = module._op(bind=False)
         key = param_key(module)
-        op.bind(key, lambda: (w, None, b), _pair_adjoint(ctx, module, "_hip_bwd_ops", "dxa", key))
+        op.bind(key, lambda: (w, None, b), _pair_adjoint(ctx, module, "dxa", key))
         if lrelu or res is not None:
             y = op.forward(x, in_act=L.IN_LRELU if lrelu else L.IN_NONE, res=None if res is None else res.contiguous().float())
         else:
@@ -94,21 +60,12 @@ class HipConvFn(torch.autograd.Function):
         return gx, gw, gb, None, None, (gy if (ctx.has_res and need[5]) else None)
 
 
-def _cached_op(holder, cache, name, *args):
-    """ConvOp handle `name` of `holder.__dict__[cache]` ("_hip_bwd_ops": the backward-data convs, next to a module's forward handles;
-    "_hip_disc_ops": the discriminator convs), created from `args` on first use"""
-    ops = holder.__dict__.setdefault(cache, {})
-    if name not in ops:
-        ops[name] = ConvOp(*args)
-    return ops[name]
-
-
-def _pair_adjoint(ctx, holder, cache, name, key):
-    """The grad-input handle `name` of `holder` (created by its first backward) when the forward's pack should fill it too -- the same weight,
+def _pair_adjoint(ctx, holder, role, key):
+    """The grad-input handle `role` of `holder` (created by its first backward) when the forward's pack should fill it too -- the same weight,
     both packs in one pair of launches (ConvOp.bind) -- else None"""
     if key is None or L.switch("VS_NO_PAIR_PACK") or not ctx.needs_input_grad[0]:
         return None
-    return holder.__dict__.get(cache, {}).get(name)
+    return handles(holder).get(role)
 
 
 def conv_backward(m, x, w, gy, need_x, need_w, key=False, need_b=None):
@@ -140,7 +97,7 @@ def conv_backward(m, x, w, gy, need_x, need_w, key=False, need_b=None):
             pb = d * (K - 1) - p
             assert pb >= 0, "conv backward-data: padding larger than the receptive field is not supported"
             # (the handle packs the adjoint -- channel transpose + tap reversal -- of the forward weight by index arithmetic)
-            op = _cached_op(m, "_hip_bwd_ops", "dxa", L.CONV1D, Cout, Cin, K, d, pb, L.CONV_ADJOINT)
+            op = handles(m).op("dxa", L.CONV1D, Cout, Cin, K, d, pb, L.CONV_ADJOINT)
             op.bind(param_key(m) if key is False else key, lambda: (w, None, None))
             gx = op.forward(gy)
     else:
@@ -153,7 +110,7 @@ def conv_backward(m, x, w, gy, need_x, need_w, key=False, need_b=None):
         gyp = F.pad(gy, (p, max(right, 0)))[:, :, :Mq * u]
         G = gyp.view(B, Cout, Mq, u).permute(0, 3, 1, 2).reshape(B, u * Cout, Mq)
         if need_x:
-            op = _cached_op(m, "_hip_bwd_ops", "dx", L.CONV1D, u * Cout, Cin, Q, 1, 0, 0)
+            op = handles(m).op("dx", L.CONV1D, u * Cout, Cin, Q, 1, 0, 0)
             op.bind(param_key(m) if key is False else key,
                     lambda: (F.pad(w.detach(), (0, Q * u - K)).view(Cin, Cout, Q, u).permute(0, 3, 1, 2).reshape(Cin, u * Cout, Q), None, None))
             gx = op.forward(G.contiguous())                                             # [B, Cin, Mq - Q + 1 = T]
@@ -192,7 +149,7 @@ class StridedConv1dFn(torch.autograd.Function):
     the gradients as zeros).  The layout changes are one launch each (vs_phase_stack from any view of x, vs_phase_items,
     vs_phase_unstack) where pad / view / permute / contiguous / zeros took 3-5.  The result is returned as the [N, Cout, Tout] VIEW of
     the engine's output sequence (the leaky_relu that follows every layer but the last writes it out contiguously).
-    `holder` caches the engine handles."""
+    `holder` (the discriminator's nn.Conv1d / nn.Conv2d) keeps the engine handles in its table (ops.handles)."""
 
     @staticmethod
     def forward(ctx, x, w, b, stride, pad, holder):
@@ -205,10 +162,10 @@ class StridedConv1dFn(torch.autograd.Function):
         XF = torch.empty((1, stride * C, Lf + Q - 1), device=x.device, dtype=torch.float32)
         L.check(lib.vs_phase_stack(ctypes.c_void_p(x.data_ptr()), x.stride(0), x.stride(1), x.stride(2), L.ptr(XF), N, C, T, stride, pad, Hq,
                                    Lf + Q - 1, L.stream_ptr()))
-        op = _cached_op(holder, "_hip_disc_ops", ("fwd", C, Cout, K, stride), L.CONV1D, stride * C, Cout, Q, 1, 0, 0)
+        op = handles(holder).op(("disc_fwd", C, Cout, K, stride), L.CONV1D, stride * C, Cout, Q, 1, 0, 0)
         key = param_key(holder)
         op.bind(key, lambda: (_phase_weights(w.detach(), stride, Q) if stride > 1 else w, None, b),
-                _pair_adjoint(ctx, holder, "_hip_disc_ops", ("dxa", C, Cout, K, stride), key))
+                _pair_adjoint(ctx, holder, ("disc_dxa", C, Cout, K, stride), key))
         yF = op.forward(XF)                                                                     # [1, Cout, N*Hq]
         ctx.save_for_backward(XF, w)
         ctx.cfg = (N, C, T, K, stride, pad, Q, Hq, Tout, b is not None, holder)
@@ -238,7 +195,7 @@ class StridedConv1dFn(torch.autograd.Function):
                 g2 = conv_wgrad(gyF, XF, Q, 1, 0)                                               # [Cout, s*C, Q]
             gw = g2.view(Cout, stride, C, Q).permute(0, 2, 3, 1).reshape(Cout, C, Q * stride)[:, :, :K].contiguous() if stride > 1 else g2
         if ctx.needs_input_grad[0]:
-            op = _cached_op(holder, "_hip_disc_ops", ("dxa", C, Cout, K, stride), L.CONV1D, Cout, stride * C, Q, 1, Q - 1, L.CONV_ADJOINT)
+            op = handles(holder).op(("disc_dxa", C, Cout, K, stride), L.CONV1D, Cout, stride * C, Q, 1, Q - 1, L.CONV_ADJOINT)
             # (the handle packs the adjoint of the phase-stacked forward weight)
             op.bind(ctx.wkey, lambda: (_phase_weights(w.detach(), stride, Q) if stride > 1 else w, None, None))
             gXF = op.forward(gyF)                                                               # [1, s*C, N*Hq + Q - 1]
@@ -642,24 +599,6 @@ class AttnCoreFn(torch.autograd.Function):
         return dq, dkk, dv, drk, drv, None, None, None, None
 
 
-class _ConvHolder:
-    """What HipConvFn / conv_backward need from a conv module, for a conv that is not a module of its own: the fused q | k | v projection of
-    an attention layer (three 1x1 convs of the same input as ONE launch forward, one grad-input conv and one weight-gradient launch)."""
-    _kind = L.CONV1D
-
-    def __init__(self, c_in, c_out, k=1, dilation=1, padding=0):
-        self.in_channels, self.out_channels = c_in, c_out
-        self.kernel_size, self.dilation, self.padding, self.stride = (k,), (dilation,), (padding,), (1,)
-
-    def _op(self, bind=False):
-        ops = self.__dict__.setdefault("_hip_ops", {})
-        if "fwd" not in ops:
-            ops["fwd"] = ConvOp(L.CONV1D, self.in_channels, self.out_channels, self.kernel_size[0], self.dilation[0], self.padding[0], 0)
-        from .modules.hipconv import apply_math
-        apply_math(self.__dict__, ops["fwd"])
-        return ops["fwd"]
-
-
 def attention(m, x, frame_mask):
     """rel_transformer.py:138-179: q/k/v/o convs on the HIP engine; the core on the streaming kernels of csrc/attention_train.hip
     (`AttnCoreFn`), or -- heads wider than 128 channels, windows wider than 7, VS_NO_TRAIN_ATTN -- as differentiable torch ops with the
@@ -670,19 +609,11 @@ def attention(m, x, frame_mask):
     if x.is_cuda and dk <= 128 and (w is None or w <= 7) and T <= 65535 and plain_core and not m.__dict__.get("store_attn", False) and not L.switch("VS_NO_TRAIN_ATTN"):
         rel_k, rel_v = (m.emb_rel_k, m.emb_rel_v) if w is not None else (None, None)
         pd = m.drop.p if m.training else 0.0
-        plain = all(not hasattr(c, "weight_g") and c.bias is not None and c.kernel_size[0] == 1 for c in (m.conv_q, m.conv_k, m.conv_v))
-        if plain and not L.switch("VS_NO_FUSED_QKV"):
+        qkv = None if L.switch("VS_NO_FUSED_QKV") else m.fused_qkv()
+        if qkv is not None:
             # q | k | v as one [3C, C_in] projection (rel_transformer.py:120-122 are three nn.Conv1d(channels, channels, 1) of the same x)
-            holder = m.__dict__.get("_hip_qkv")
-            if holder is None:
-                holder = m.__dict__["_hip_qkv"] = _ConvHolder(m.conv_q.in_channels, 3 * C)
-                holder._key_sources = (m.conv_q, m.conv_k, m.conv_v)
-            arith = m.conv_q.__dict__.get("_hip_math")
-            if arith is not None:
-                holder.__dict__["_hip_math"] = arith
-            wqkv = torch.cat([m.conv_q.weight, m.conv_k.weight, m.conv_v.weight], 0)
-            bqkv = torch.cat([m.conv_q.bias, m.conv_k.bias, m.conv_v.bias], 0)
-            out = AttnCoreFn.apply(HipConvFn.apply(x, wqkv, bqkv, holder, False, None), None, None, rel_k, rel_v, frame_mask, nh, w if w is not None else -1, pd)
+            wqkv, _, bqkv = qkv.weights()
+            out = AttnCoreFn.apply(HipConvFn.apply(x, wqkv, bqkv, qkv, False, None), None, None, rel_k, rel_v, frame_mask, nh, w if w is not None else -1, pd)
         else:
             out = AttnCoreFn.apply(conv(m.conv_q, x), conv(m.conv_k, x), conv(m.conv_v, x), rel_k, rel_v, frame_mask, nh,
                                    w if w is not None else -1, pd)

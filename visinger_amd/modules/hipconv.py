@@ -6,12 +6,15 @@ They ARE torch.nn.Conv1d / ConvTranspose1d subclasses, so construction, default 
 ``run(...)`` to fuse their elementwise neighbours (activation, mask, residual, gate, coupling) into the conv.
 
 Training mode (autograd enabled) is served by visinger_amd.autograd: HIP forward for the convs, PyTorch-ROCm backward.
+
+The engine handles of a module are process-local and live in its visinger_amd.ops.HandleTable, which copies and pickles as an empty
+table; the settings `_hip_math` / `_hip_math_auto` / `_hip_storage` in the module's ``__dict__`` travel with the module.
 """
 import torch
 import torch.nn as nn
 
 from .. import _lib as L
-from ..ops import ConvOp
+from ..ops import handles
 
 
 def _forward_only_guard(module):
@@ -53,17 +56,16 @@ class _HipConvMixin:
         bind=False returns the handle without (re)packing the module's parameters (the autograd path packs the live
         folded weight itself)."""
         kind = self._kind if kind is None else kind
-        ops = self.__dict__.setdefault("_hip_ops", {})
-        key = (kind, flags)
-        if key not in ops:
+        table, role = handles(self), ("fwd", kind, flags)
+        op = table.get(role)
+        if op is None:
             if self._kind == L.CONV_TRANSPOSE1D:
-                ops[key] = ConvOp(L.CONV_TRANSPOSE1D, self.in_channels, self.out_channels, self.kernel_size[0],
-                                  self.stride[0], self.padding[0], flags)
+                op = table.op(role, L.CONV_TRANSPOSE1D, self.in_channels, self.out_channels, self.kernel_size[0],
+                              self.stride[0], self.padding[0], flags)
             else:
                 assert self.stride[0] == 1 and self.groups == 1, "HIP conv engine: stride-1 ungrouped convs only"
-                ops[key] = ConvOp(kind, self.in_channels, self.out_channels, self.kernel_size[0],
-                                  self.dilation[0], self.padding[0], flags)
-        op = ops[key]
+                op = table.op(role, kind, self.in_channels, self.out_channels, self.kernel_size[0],
+                              self.dilation[0], self.padding[0], flags)
         apply_math(self.__dict__, op)
         if bind:
             w, g = self._weights()
@@ -80,9 +82,6 @@ class _HipConvMixin:
             from ..autograd import conv
             return conv(self, x)
         return self.run(x.contiguous().float())
-
-    def __getstate__(self):                      # handles are process-local (forward, backward-data and discriminator caches)
-        return drop_process_local_state(self.__dict__.copy())
 
     def _load_from_state_dict(self, *args, **kwargs):
         """nn.Module's loader for this conv's own tensors, then the weight-range check of INTEGRATION.md 4 on what was loaded (round 6): a real checkpoint whose
@@ -189,29 +188,14 @@ def select_math_by_weight_range(module, max_row_drop_bits=10.0, fallback=None):
 
 
 def repack_weights(module):
-    """Drop every packed-weight cache under `module`: the next forward re-folds and re-packs from the live parameters.  The
-    cache key (data_ptr, in-place version) of visinger_amd.ops.ConvOp.set_weights follows optimizer steps, ``load_state_dict``
-    and ``copy_`` on the parameter itself, but NOT edits made through ``p.data`` (EMA swaps, manual re-initialisation: `.data`
-    carries its own version counter) -- call this after such an edit."""
+    """Forget the packed-weight key of every handle under `module` (forward, grad-input and discriminator convs, the attention layers' fused
+    q | k | v projections: visinger_amd.ops.HandleTable): the next forward re-folds and re-packs from the live parameters.  The cache key
+    (data_ptr, in-place version) of visinger_amd.ops.ConvOp.set_weights follows optimizer steps, ``load_state_dict`` and ``copy_`` on the
+    parameter itself, but NOT edits made through ``p.data`` (EMA swaps, manual re-initialisation: `.data` carries its own version counter)
+    -- call this after such an edit."""
     for m in module.modules():
-        for key in ("_hip_ops", "_hip_bwd_ops", "_hip_disc_ops"):
-            for op in m.__dict__.get(key, {}).values():
-                op.invalidate()
-        for key in DERIVED_CACHES:      # handles keyed on (data_ptr, _version) of SEVERAL parameters: rebuilt from the live ones
-            m.__dict__.pop(key, None)
+        handles(m).invalidate()
     return module
-
-
-# per-module caches derived from more than one parameter (MultiHeadAttention: the fused q | k | v projection of the inference path,
-# its training twin): dropped by repack_weights and never pickled
-DERIVED_CACHES = ("_hip_qkv_inf", "_hip_qkv")
-
-
-def drop_process_local_state(state):
-    """__getstate__ helper: remove conv handles and derived caches (ctypes handles) from a module's __dict__ copy"""
-    for key in ("_hip_ops", "_hip_bwd_ops", "_hip_disc_ops") + DERIVED_CACHES:
-        state.pop(key, None)
-    return state
 
 
 def mask2d(x_mask, B, T):

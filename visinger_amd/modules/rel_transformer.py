@@ -16,8 +16,8 @@ from torch import nn
 
 from .. import _lib as L
 from .. import autograd
-from ..ops import ConvOp, layernorm_c, rel_attention, _off
-from .hipconv import HipConv1d, mask2d, _forward_only_guard, drop_process_local_state
+from ..ops import HANDLES, handles, layernorm_c, param_key, rel_attention, _off
+from .hipconv import HipConv1d, mask2d, _forward_only_guard
 
 
 class LayerNorm(nn.Module):
@@ -77,6 +77,33 @@ class SinusoidalPositionalEmbedding(nn.Module):
         return torch.nn.functional.embedding(positions.reshape(-1), self.weights).view(bsz, seq_len, -1).detach()
 
 
+class _FusedQKV:
+    """conv_q | conv_k | conv_v of one attention layer as ONE [3C, C] projection (three nn.Conv1d(channels, channels, 1) of the same input in
+    self-attention, rel_transformer.py:120-122, 141-143; rows are independent: same sums): what autograd.HipConvFn / conv_backward need from a conv
+    module, for a conv that is not a module of its own -- one launch forward, one grad-input conv and one weight-gradient launch.  Inference and training
+    share it: its handles (the forward projection and, after the first backward, its VS_CONV_ADJOINT twin) live in the ATTENTION module's table, where
+    repack_weights and copies find them like any conv's; their key is param_key over the three source convs."""
+    _kind, dilation, padding = L.CONV1D, (1,), (0,)
+
+    def __init__(self, att):
+        self._key_sources = (att.conv_q, att.conv_k, att.conv_v)
+        self.__dict__[HANDLES] = handles(att)
+
+    def _op(self, bind=False):
+        """the forward handle, on the arithmetic of conv_q's (the attention core follows the same one); never bound here: the callers bind weights()"""
+        q = self._key_sources[0]
+        op = handles(self).op(("fwd", L.CONV1D, 0), L.CONV1D, q.in_channels, 3 * q.out_channels, 1, 1, 0)
+        arith = q._op(bind=False).math
+        if op.math != arith:
+            op.set_math(arith)         # (vs_conv_set_math re-packs the planes from the fp32 fragments the handle keeps: the key stays)
+        return op
+
+    def weights(self):
+        """(w, None, bias) of the projection, as ConvOp.bind's derive() returns them; differentiable in the six parameters"""
+        convs = self._key_sources
+        return torch.cat([cv.weight for cv in convs], 0), None, torch.cat([cv.bias for cv in convs], 0)
+
+
 class MultiHeadAttention(nn.Module):
     """rel_transformer.py:103-254"""
 
@@ -117,31 +144,15 @@ class MultiHeadAttention(nn.Module):
             self.conv_k.bias.data.copy_(self.conv_q.bias.data)
         nn.init.xavier_uniform_(self.conv_v.weight)
 
-    def __getstate__(self):      # the fused q | k | v handles are process-local caches
-        return drop_process_local_state(self.__dict__.copy())
-
-    def _fused_qkv_op(self):
-        """One conv handle for conv_q | conv_k | conv_v (three nn.Conv1d(channels, channels, 1) of the same input in self-attention,
-        rel_transformer.py:120-122, 141-143): the weights are concatenated and packed once per version of the six parameters."""
-        convs = (self.conv_q, self.conv_k, self.conv_v)
-        if any(hasattr(cv, "weight_g") or cv.bias is None for cv in convs):
+    def fused_qkv(self):
+        """The fused q | k | v projection of this layer (_FusedQKV, created once), or None where the three convs stay separate launches: a weight-normed
+        conv (its fold is per conv), a conv without bias, a kernel wider than 1."""
+        if any(hasattr(cv, "weight_g") or cv.bias is None or cv.kernel_size[0] != 1 for cv in (self.conv_q, self.conv_k, self.conv_v)):
             return None
-        params = [t for cv in convs for t in (cv.weight, cv.bias)]
-        math = self.conv_q._op(bind=False).math
-        key = tuple((t.data_ptr(), t._version) for t in params) + (math,)
-        op = self.__dict__.get("_hip_qkv_inf")
-        if op is None:
-            op = self.__dict__["_hip_qkv_inf"] = ConvOp(L.CONV1D, self.channels, 3 * self.channels, 1, 1, 0)
-
-        def derive():
-            if op.math != math:
-                op.set_math(math)
-            w = torch.cat([cv.weight.detach() for cv in convs], 0).contiguous()
-            b = torch.cat([cv.bias.detach() for cv in convs], 0).contiguous()
-            return w, None, b
-
-        op.bind(key, derive)
-        return op
+        qkv = self.__dict__.get("_qkv")
+        if qkv is None:
+            qkv = self.__dict__["_qkv"] = _FusedQKV(self)
+        return qkv
 
     def forward(self, x, c, attn_mask=None, frame_mask=None, in_mask=False):
         """x, c: [B, C, T].  attn_mask: the reference's [B, 1, T, T] mask, which RelativeEncoder always builds as
@@ -172,9 +183,11 @@ class MultiHeadAttention(nn.Module):
         c = x if c is x else c.contiguous().float()
         qkv = torch.empty((B, 3 * C, T), device=x.device, dtype=torch.float32)
         ia = L.IN_MASK if in_mask else L.IN_NONE
-        fused = self._fused_qkv_op() if (c is x and not L.switch("VS_NO_FUSED_QKV")) else None
+        fused = self.fused_qkv() if (c is x and not L.switch("VS_NO_FUSED_QKV")) else None
         if fused is not None:
-            fused.forward(x, in_act=ia, mask=m2, y=qkv)       # q | k | v: ONE [3C, C] projection of the same x (rows are independent: same sums)
+            op = fused._op()
+            op.bind(param_key(fused), fused.weights)
+            op.forward(x, in_act=ia, mask=m2, y=qkv)
         else:
             for j, (conv, src) in enumerate(((self.conv_q, x), (self.conv_k, c), (self.conv_v, c))):
                 conv.run(src, in_act=ia, mask=m2, y_ptr=_off(qkv, j * C * T), y_bs=3 * C * T)

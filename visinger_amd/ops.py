@@ -175,13 +175,6 @@ class ConvOp:
         """Kernel instance this handle's most recent forward() was dispatched to ("" before the first launch)."""
         return self._last_kernel
 
-    def wino_eligible(self):
-        """mirrors vs_conv_create: stride-1 'same' conv, odd k >= 3, dilation 1/3/5, whole 32-row tiles -> F(2,3) path
-        (taken by vs_conv_forward unless the call splits rows or uses a coupling output mode)"""
-        k, d = self.k, self.dil
-        return (self.kind == L.CONV1D and k >= 3 and k % 2 == 1 and d in (1, 3, 5) and self.pad == d * (k - 1) // 2 and
-                self.c_out % 32 == 0 and 3 * -(-k // 3) * d <= 64)
-
     def algorithmic_flops(self, B, T):
         """2*MAC of the convolution itself (what torch.utils.flop_counter reports for the reference's op)."""
         if self.kind == L.CONV_TRANSPOSE1D:
@@ -207,7 +200,7 @@ class ConvOp:
 
     def bind(self, key, derive, adjoint=None):
         """Pack the weights identified by `key` unless this handle already carries them.  -> True when it packed.
-        key: whatever identifies the PARAMETERS the weight derives from, compared by == -- autograd.param_key: their (data_ptr, in-place
+        key: whatever identifies the PARAMETERS the weight derives from, compared by == -- param_key: their (data_ptr, in-place
         version) tuples -- or None when nothing does (spectral norm: a power iteration per forward; VS_NO_PACK_CACHE): None always packs.
         derive() -> (w, g, bias) as set_weights takes them, temporaries included; called only when the handle is stale, so the derivation
         (a phase-stacked or concatenated weight) costs nothing otherwise.  Within one optimizer step the same parameters reach a handle
@@ -306,6 +299,76 @@ def _rebuild_conv_op(args, math):
     op.kind, op.c_in, op.c_out, op.k, op.dil, op.pad, op.flags = args
     op._h, op._pending_math, op._wkey, op._last_kernel = None, math, None, ""
     return op
+
+
+_WEIGHT_EPOCH = [0]
+
+
+def bump_weight_epoch():
+    """Invalidate every packed-weight key at once (the epoch is part of each key).  (data_ptr, _version) follows optimizer steps,
+    load_state_dict and copy_ on the parameter, but NOT edits made through ``p.data`` (EMA swaps, ``p.data.clamp_``: `.data` carries
+    its own version counter).  VISingerTrainer.training_step bumps the epoch once per step, so such an edit between two steps costs one
+    re-pack instead of silently training on stale packed weights; inside a step the cache still serves the frozen network's second use."""
+    _WEIGHT_EPOCH[0] += 1
+
+
+def param_key(holder):
+    """Identity and in-place versions of the PARAMETERS the live weight / bias of a conv holder derive from: (weight_v, weight_g) under
+    torch.nn.utils.weight_norm, else the plain weight parameter; None when the weight is not a function of parameters alone (spectral
+    norm runs a power iteration per forward).  Optimizer steps, load_state_dict and every other in-place write bump the versions; a
+    handle whose packed weights carry the same key need not be packed again (ConvOp.bind)."""
+    if L.switch("VS_NO_PACK_CACHE"):
+        return None
+    sources = holder.__dict__.get("_key_sources")
+    if sources is not None:                   # a fused projection (an attention layer's q | k | v): the concatenation of several modules' weights
+        keys = tuple(param_key(m_) for m_ in sources)
+        return None if any(k is None for k in keys) else keys
+    if not isinstance(holder, torch.nn.Module):
+        return None
+    if hasattr(holder, "weight_g") and hasattr(holder, "weight_v"):
+        ps = (holder.weight_v, holder.weight_g)
+    elif isinstance(holder._parameters.get("weight"), torch.nn.Parameter):
+        ps = (holder.weight,)
+    else:
+        return None
+    bias = getattr(holder, "bias", None)
+    return tuple((t.data_ptr(), t._version) for t in ps) + (None if bias is None else (bias.data_ptr(), bias._version), _WEIGHT_EPOCH[0])
+
+
+class HandleTable(dict):
+    """{role: ConvOp}: every process-local handle of ONE holder -- a HipConv1d / HipConvTranspose1d, a stock nn.Conv1d / nn.Conv2d of the discriminators,
+    an attention layer (its fused q | k | v projection).  Roles: ("fwd", kind, flags) the forward convs; "dxa" / "dx" the grad-input convs of a conv / a
+    transposed conv; ("disc_fwd" | "disc_dxa", C, Cout, K, stride) the discriminators' phase-stacked convs.  `.get(role)` looks one up without creating it.
+    A vs_conv_t is never pickled and never shared by two owners: a copy of the table (copy.deepcopy of a module for an EMA model, torch.save(module),
+    pickling for a spawned worker) is EMPTY, and the copy's owner creates and binds its own handles on first use."""
+
+    def op(self, role, *args):
+        """the handle of `role`, created as ConvOp(*args) on first use"""
+        if role not in self:
+            self[role] = ConvOp(*args)
+        return self[role]
+
+    def invalidate(self):
+        """forget the packed-weight key of every handle (ConvOp.invalidate)"""
+        for op in self.values():
+            op.invalidate()
+
+    def __reduce__(self):
+        return (HandleTable, ())
+
+    def __deepcopy__(self, memo):
+        return HandleTable()
+
+
+HANDLES = "_hip_handles"
+
+
+def handles(holder):
+    """the HandleTable of `holder`, kept in its __dict__ (beside an nn.Module's attribute machinery: no parameter, buffer or state_dict entry)"""
+    table = holder.__dict__.get(HANDLES)
+    if table is None:
+        table = holder.__dict__[HANDLES] = HandleTable()
+    return table
 
 
 def weightnorm_fold(v, g):

@@ -253,7 +253,7 @@ class VISingerTrainer(nn.Module):
         return n, first, last
 
     def _training_step(self, batch, runner=None):
-        from .autograd import bump_weight_epoch
+        from .ops import bump_weight_epoch
         bump_weight_epoch()      # edits made through p.data since the last step (EMA swaps) must not meet a stale packed weight
         # (parameter-level surgery without a train() / eval() toggle -- remove_weight_norm, added or swapped parameters -- must not leave the cached
         #  parameter lists and weight banks acting on orphaned Parameters)

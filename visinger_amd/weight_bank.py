@@ -15,13 +15,14 @@ adjoint handle of its grad-input).  Per training step that was 256 + 182 weight-
 * two launches pack every conv handle whose packed weights are stale (vs_conv_set_weights_batch).
 
 The modules then find their weight in ``module.__dict__["_w_eff"]`` (autograd.effective_weight, discriminator._live_params) and their
-handles already carrying the pass's key; ``release()`` removes the entries again, so a forward outside a bank-managed pass (eval, tests
-that call modules directly) takes the per-module path as before.  ``VS_NO_WEIGHT_BANK=1`` is the A/B switch (train.VISingerTrainer).
+handles (visinger_amd.ops.handles(module): the forward conv and the grad-input conv of its table) already carrying the pass's key;
+``release()`` removes the ``_w_eff`` entries again, so a forward outside a bank-managed pass (eval, tests that call modules directly)
+takes the per-module path as before.  ``VS_NO_WEIGHT_BANK=1`` is the A/B switch (train.VISingerTrainer).
 """
 import torch
 
 from . import _lib as L
-from .ops import ConvOp
+from .ops import ConvOp, handles, param_key
 
 
 class _BatchedWeightNorm(torch.autograd.Function):
@@ -141,7 +142,6 @@ class WeightBank:
     def refresh(self):
         """Fold every weight-normed weight of the network (one differentiable node) and pack the stale conv handles.  Call at the top of
         a training pass, AFTER requires_grad of the network's parameters is what the pass needs; `release()` when the forward is done."""
-        from .autograd import param_key
         st = self._scan()
         self._gen += 1
         st["gen"] = self._gen
@@ -160,7 +160,8 @@ class WeightBank:
             self._live = st["mods"]
         jobs = []
         for m in st["convs"]:
-            op = m.__dict__.get("_hip_ops", {}).get((m._kind, 0))
+            table = handles(m)
+            op = table.get(("fwd", m._kind, 0))
             if op is None:                 # (first pass: the module's forward creates the handle and packs it)
                 continue
             key = param_key(m)
@@ -174,7 +175,7 @@ class WeightBank:
                 w = m.weight
             if not op.has_weights_of(key):
                 jobs.append((op, w, m.bias, key))
-            adj = m.__dict__.get("_hip_bwd_ops", {}).get("dxa")
+            adj = table.get("dxa")
             if adj is not None and not adj.has_weights_of(key):
                 jobs.append((adj, w, None, key))
         ConvOp.set_weights_batch(jobs)
