@@ -321,6 +321,20 @@ def test_conv_engine_random_sweep(seed, monkeypatch, vs_option):
     conv_fuzz.main()          # (sets VS_WINO_FORCE per case through L.set_option; the fixture restores it)
 
 
+@pytest.mark.parametrize("math", [L.MATH_BF16, L.MATH_SPLIT3], ids=["bf16", "split3"])
+def test_conv_engine_random_sweep_pinned(math, monkeypatch, vs_option):
+    """the same sweep in the two arithmetics its own draw never takes: plain bf16 (against the oracle on bf16-rounded operands, tests/bf16_reference.py) and the
+    default split-f16 x3, each at the sweep's 3e-5 -- 100 cases, pinned through VS_CONV_MATH"""
+    import os
+    import sys
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
+    import conv_fuzz
+    monkeypatch.setattr(sys, "argv", ["conv_fuzz.py", "100", "13"])
+    vs_option("VS_WINO_FORCE", 0)
+    vs_option("VS_CONV_MATH", math)
+    conv_fuzz.main()
+
+
 @pytest.mark.parametrize("C,k,d,T,B", [(32, 3, 1, 2048, 2), (32, 7, 3, 1500, 1), (32, 11, 5, 1024, 2), (64, 3, 5, 1000, 1),
                                         (64, 7, 1, 700, 2), (64, 11, 3, 516, 1), (32, 5, 1, 37, 1), (32, 3, 3, 4, 2), (64, 9, 1, 250, 1)])
 @pytest.mark.parametrize("math", [L.MATH_SPLIT6, L.MATH_F32, L.MATH_BF16])
