@@ -38,7 +38,7 @@ VS_API const char *vs_last_error(void);
  * this library, so a caller that attributes per-launch timings to kernel instances (bench.py's roofline line) reads it back
  * here instead of restating the selection.  Thread-local; "" before the first launch.  (No reference counterpart.)          */
 VS_API const char *vs_last_kernel_name(void);
-VS_API int vs_abi_version(void);          /* 7: vs_f0_norm_interp, vs_pitch_condition, vs_normal_fill, vs_prior_sample (appended to 7: new exports only, no layout or signature changed),vs_conv_set_weights_batch, vs_weight_norm_multi_fwd / _bwd, vs_conv_wgrad_bias, vs_wn_step_fwd / _bwd, vs_l1_mean_fwd / _bwd; 6: vs_source_hash, vs_bias_grad, vs_conv_set_weights_pair; 5: vs_relattn_fwd_work / vs_relattn_kv_work_bytes; 4: vs_set_option / vs_get_option / vs_reset_option; 3: vs_dtype in vs_conv_io_t; 2: vs_relattn_fwd(math) */
+VS_API int vs_abi_version(void);          /* 7: vs_retime_tokens, vs_retime_frames, vs_f0_norm_interp, vs_pitch_condition, vs_normal_fill, vs_prior_sample (appended to 7: new exports only, no layout or signature changed),vs_conv_set_weights_batch, vs_weight_norm_multi_fwd / _bwd, vs_conv_wgrad_bias, vs_wn_step_fwd / _bwd, vs_l1_mean_fwd / _bwd; 6: vs_source_hash, vs_bias_grad, vs_conv_set_weights_pair; 5: vs_relattn_fwd_work / vs_relattn_kv_work_bytes; 4: vs_set_option / vs_get_option / vs_reset_option; 3: vs_dtype in vs_conv_io_t; 2: vs_relattn_fwd(math) */
 /* sha256 (hex) over the sources this library was compiled from (kernels, headers, textual includes, the build recipe), embedded by
  * visinger_amd/csrc/build.py.  The loader recomputes it over the tree it sits in and refuses a library built from other sources (a
  * stale object that an mtime check would pass after a checkout).  (No reference counterpart: the reference has no native code.)  */
@@ -369,6 +369,34 @@ VS_API int vs_prior_sample(const float *mu, const float *logs, int64_t stat_batc
 VS_API int vs_f0_norm_interp(const float *f0_hz, const int64_t *lengths, float *f0_norm, float *uv, int64_t B, int64_t T, void *stream);
 VS_API int vs_pitch_condition(const float *pred, const float *f0_norm, const float *uv, const float *mask, const float *cents, float *cond,
                               float *f0_hz_out, int64_t B, int64_t T, void *stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * f5  tempo and duration control of synthesis (csrc/timing_ops.hip): the frame alignment, and a curve on its timeline, retimed on
+ *     the device.  Not in the reference (no length regulator; its inference replays the score's timing).  Per item b, tokens i = 1 .. T_tokens:
+ *     vs_retime_tokens: d_i = frames of mel2ph[b] equal to i (0 and indices above T_tokens are ignored, as in vs_mel2token_to_dur), or dur[b, i-1]
+ *       clamped to [0, 2^24) -- exactly one of mel2ph [B, T_frames] / dur [B, T_tokens] is given;  c_i = d_1 + .. + d_i.
+ *       f = stretch[b, i-1] / tempo[b] (one fp32 division; NULL stretch / tempo = 1), a non-finite f becomes 1, then f is clamped to [2^-6, 2^6];
+ *       s_i = (int64) rintf(f * 65536);  P_i = sum_{j<=i} d_j s_j;  R_i = (P_i + 32768) >> 16;  m_i = d_i > 0 ? min_frames : 0;
+ *       e_0 = 0, e_i = max(e_{i-1} + m_i, R_i): cumulative rounding with a floor -- with min_frames = 1 a token that had frames keeps one, an
+ *       empty token stays empty, all factors 1 give e = c.  cum_old = c, cum_new = e (int64 [B, T_tokens]), lengths[b] = e_T, or
+ *       min(e_T, max_frames) with max_frames > 0 (0 = no capacity).  mel2ph must be monotonic over its valid prefix (not checked).
+ *       One workgroup per item: integer LDS histogram, then a chunked int64 scan (the recurrence in its closed form M_i + max(0, max_{j<=i}(R_j - M_j)),
+ *       M the prefix sum of m); bit-reproducible, independent of the launch shape.  stretch, tempo, lengths: DEVICE buffers, read by the kernel.
+ *     vs_retime_frames: for t < min(lengths[b], T_out): mel2ph_out[b, t] = the smallest i with e_i > t (upper bound in the row of cum_new); 0 beyond.
+ *       curve (optional, fp32 [B, curve_T] on the OLD timeline, <= 0 = unvoiced) -> curve_out [B, T_out]: for frame t of token i, u = t - e_{i-1},
+ *       n = d_i, n' = e_i - e_{i-1}:  num = (2u + 1) n - n', den = 2 n';  num < 0: k = 0, w = 0, else k = num / den, w = float(num - k den) / float(den);
+ *       k >= n - 1: k = n - 1, w = 0;  a = curve[c_{i-1} + k], b = curve[c_{i-1} + min(k + 1, n - 1)];  both > 0: a + w (b - a), else a if w < 0.5 else b
+ *       (an unvoiced frame is never blended; w = 0 copies a's bits; no read across a token boundary; an index outside [0, curve_T) reads as 0).
+ *       0 beyond lengths[b].  One lane per new frame.
+ *     VS_EINVAL before anything is launched: both or neither of mel2ph / dur, NULL outputs, aliased dur / cum_old / cum_new, B, T_tokens, T_out <= 0,
+ *     T_tokens > 8192 (the LDS histogram), T_frames outside [1, 2^24) with mel2ph, min_frames outside [0, 65536], max_frames < 0, curve without
+ *     curve_out or the reverse, curve_T <= 0 with a curve, T_out >= 2^31.  No allocation, no host synchronisation: a captured graph replays under
+ *     another tempo / stretch by overwriting those buffers, inside the capacity max_frames = T_out.                                      */
+VS_API int vs_retime_tokens(const int64_t *mel2ph, const int64_t *dur, const float *stretch, const float *tempo, int64_t min_frames,
+                            int64_t max_frames, int64_t *cum_old, int64_t *cum_new, int64_t *lengths, int64_t B, int64_t T_frames,
+                            int64_t T_tokens, void *stream);
+VS_API int vs_retime_frames(const int64_t *cum_old, const int64_t *cum_new, const int64_t *lengths, const float *curve, int64_t curve_T,
+                            int64_t *mel2ph_out, float *curve_out, int64_t B, int64_t T_tokens, int64_t T_out, void *stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * a13 grouped / strided Conv1d of the scale discriminator (modules/discriminator.py:55-60) and its gradients.

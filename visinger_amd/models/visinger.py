@@ -15,13 +15,16 @@ counter-based streams on the device instead (visinger_amd/sampling.py): an item'
 Pitch control (not in the reference; visinger_amd/pitch.py): ``f0_hz`` is a guide curve in Hz per frame (0 = unvoiced), normalised
 and gap-interpolated on the device; ``voicing`` takes the voiced frames from the guide or from the predictor; ``pitch_shift_cents`` transposes
 the conditioning curve per item; ``ret["f0_hz"]`` is then the curve the prior was conditioned on, in Hz.
+
+Tempo control (not in the reference; visinger_amd/timing.py): ``tempo`` (per item) and ``ph_stretch`` (per token) retime ``mel2ph`` on the
+device before anything else runs, and warp ``f0_hz`` along with it; ``ret["mel2ph"]`` / ``ret["frame_lengths"]`` are the alignment that was sung.
 """
 from copy import deepcopy
 
 import torch
 import torch.nn as nn
 
-from .. import pitch, sampling
+from .. import pitch, sampling, timing
 from ..modules.commons.utils import Embedding, rand_slice_segments, slice_segments
 from ..modules.discriminator import DiscriminatorP, DiscriminatorS
 from ..modules.rel_transformer import SinusoidalPositionalEmbedding
@@ -129,7 +132,11 @@ class VISinger(nn.Module):
 
     def forward(self, text_tokens, pitch_tokens, dur_tokens, mel2ph, spk_embed=None, spk_id=None, f0=None, uv=None,
                 mel=None, infer=False, noise=None, noise_q=None, u_slice=None, mask_decoder=False, seeds=None, takes=1, first_take=0,
-                noise_scale=1.0, f0_hz=None, voicing="guide", pitch_shift_cents=None, **kwargs):
+                noise_scale=1.0, f0_hz=None, voicing="guide", pitch_shift_cents=None, tempo=None, ph_stretch=None, max_frames=None, **kwargs):
+        """tempo / ph_stretch / max_frames (synthesis only): mel2ph is retimed on the device by ph_stretch[b, i] / tempo[b] per token (timing.retime; tempo: a
+        number, one per item, or an fp32 GPU tensor [B]; ph_stretch: fp32 [B, T_ph]) and f0_hz, a curve on the old timeline, is warped with it; the step then runs
+        on the retimed alignment.  max_frames: the frame capacity of the result (items are cut at it, nothing is read back on the host: graph-capturable);
+        None = the longest retimed item, one host synchronisation.  An injected `noise` must have the new frame count; dur_tokens stay the caller's."""
         if voicing not in ("guide", "model"):
             raise ValueError(f"voicing must be 'guide' or 'model', got {voicing!r}")
         pitch_edit = None
@@ -147,6 +154,18 @@ class VISinger(nn.Module):
         elif takes != 1 or first_take != 0 or noise_scale != 1.0:
             raise ValueError("takes / first_take / noise_scale belong to the seeded path: give seeds")
         ret = {}
+        if tempo is not None or ph_stretch is not None:
+            if not infer:
+                raise ValueError("tempo / ph_stretch apply to the synthesis path only (infer=True)")
+            if f0 is not None or uv is not None:
+                raise ValueError("tempo / ph_stretch cannot retime f0 / uv (normalised curves on the old timeline): give the guide as f0_hz")
+            mel2ph, ret["frame_lengths"], f0_hz = timing.retime(mel2ph=mel2ph, T_ph=text_tokens.shape[1], stretch=ph_stretch, tempo=tempo,
+                                                                max_frames=max_frames, curve=f0_hz)
+            ret["mel2ph"] = mel2ph
+            if pitch_edit is not None:
+                pitch_edit = (f0_hz, voicing, pitch_shift_cents)
+        elif max_frames is not None:
+            raise ValueError("max_frames is the frame capacity of a retimed call: give tempo or ph_stretch")
         frame_mask, spk, mu_p, logs_p = self._prior(text_tokens, pitch_tokens, dur_tokens, mel2ph, spk_embed, spk_id, f0, uv, ret, pitch_edit)
         if infer:
             self._sample_and_decode(frame_mask, spk, mu_p, logs_p, noise, ret, mask_decoder=mask_decoder, seeds=seeds, takes=takes,

@@ -5,7 +5,7 @@ int16).  Host-side plumbing only."""
 import numpy as np
 import torch
 
-from . import pitch, sampling
+from . import pitch, sampling, timing
 
 
 def bucket_by_length(lengths, max_frames_per_batch, max_items_per_batch=256, keys=None):
@@ -116,7 +116,11 @@ class GraphedStep:
     are launch arguments: fixed by the capture.
     Pitch control: a batch with "f0_hz" (collate) is synthesised on that guide curve -- it sits among the static inputs like the tokens, so a replay under
     another curve is that buffer overwritten; cents= (anything pitch.cents_tensor takes) becomes a static fp32 [B] buffer the kernel reads, overwritten by
-    __call__(cents=).  `voicing` is fixed by the capture.  With either, `f0_hz_out` is the static [B, T] buffer of the sung curve in Hz."""
+    __call__(cents=).  `voicing` is fixed by the capture.  With either, `f0_hz_out` is the static [B, T] buffer of the sung curve in Hz.
+    Tempo control: tempo= (anything timing.factor_tensor takes) and ph_stretch= (fp32 [B, T_ph]) become static device buffers the retiming kernels read,
+    overwritten by __call__(tempo=, ph_stretch=); max_frames is required with either: the frame capacity fixed by the capture (the step runs max_frames
+    frames wide, an item is cut at it, `noise` has that many frames).  `frame_lengths_out` is the static int64 [B] buffer of the retimed lengths and
+    `mel2ph_out` the retimed alignment."""
 
     @staticmethod
     def fingerprint(model):
@@ -124,9 +128,12 @@ class GraphedStep:
         through `.data`, like the packed-weight caches: call hipconv.repack_weights AND drop the graphs after such an edit)"""
         return tuple((p.data_ptr(), p._version) for p in model.parameters())
 
-    def __init__(self, model, batch, noise, mask_decoder, seeds=None, takes=1, first_take=0, noise_scale=1.0, voicing="guide", cents=None):
+    def __init__(self, model, batch, noise, mask_decoder, seeds=None, takes=1, first_take=0, noise_scale=1.0, voicing="guide", cents=None, tempo=None,
+                 ph_stretch=None, max_frames=None):
         if seeds is not None and noise is not None:
             raise ValueError("seeds and noise are two sources of the same sample: give one of them")
+        if (tempo is not None or ph_stretch is not None) != (max_frames is not None):
+            raise ValueError("tempo / ph_stretch need max_frames (the frame capacity the capture fixes), and max_frames needs one of them")
         self.weights = self.fingerprint(model)       # a replay never re-folds / re-packs weights: the graph is only valid for these
         self.static = {k: v.clone() for k, v in batch.items()}
         self.noise = None if seeds is not None else noise.clone()
@@ -136,12 +143,19 @@ class GraphedStep:
         self.f0_hz_out = None
         if "f0_hz" in batch or self.cents is not None:
             sample.update(f0_hz=self.static.get("f0_hz"), voicing=voicing, pitch_shift_cents=self.cents)
+        B, dev = batch["mel2ph"].shape[0], batch["mel2ph"].device
+        self.tempo = None if tempo is None else timing.factor_tensor(tempo, B, dev).clone()
+        self.ph_stretch = None if ph_stretch is None else timing.stretch_tensor(ph_stretch, B, batch["text_tokens"].shape[1], dev).clone()
+        self.frame_lengths_out = self.mel2ph_out = None
+        if max_frames is not None:
+            sample.update(tempo=self.tempo, ph_stretch=self.ph_stretch, max_frames=int(max_frames))
 
         def run():
             b = self.static
             ret = model(b["text_tokens"], b["pitch_tokens"], b["dur_tokens"], b["mel2ph"], spk_id=b["spk_id"], infer=True,
                         mask_decoder=mask_decoder, **sample)
             self.f0_hz_out = ret.get("f0_hz")
+            self.frame_lengths_out, self.mel2ph_out = ret.get("frame_lengths"), ret.get("mel2ph")
             return ret["wav_out"]
 
         side = torch.cuda.Stream()
@@ -153,13 +167,19 @@ class GraphedStep:
         with torch.cuda.graph(self.graph):
             self.out = run()
 
-    def __call__(self, batch, noise, seeds=None, cents=None):
+    def __call__(self, batch, noise, seeds=None, cents=None, tempo=None, ph_stretch=None):
         if (self.seeds is None) != (seeds is None) or (self.noise is None) != (noise is None):
             raise ValueError("a graph captured with noise is replayed with noise, one captured with seeds with seeds")
         if ("f0_hz" in batch) != ("f0_hz" in self.static) or (self.cents is None) != (cents is None):
             raise ValueError("a graph is replayed with the inputs it was captured with (guide curve and pitch shift included)")
+        if (self.tempo is None) != (tempo is None) or (self.ph_stretch is None) != (ph_stretch is None):
+            raise ValueError("a graph captured with a tempo / token stretch is replayed with one (and one captured without, without)")
         for k, v in batch.items():
             self.static[k].copy_(v)
+        if self.tempo is not None:
+            self.tempo.copy_(timing.factor_tensor(tempo, self.tempo.shape[0], self.tempo.device))
+        if self.ph_stretch is not None:
+            self.ph_stretch.copy_(timing.stretch_tensor(ph_stretch, *self.ph_stretch.shape, self.ph_stretch.device))
         if self.cents is not None:
             self.cents.copy_(pitch.cents_tensor(cents, self.cents.shape[0], self.cents.device))
         if self.seeds is not None:
@@ -170,9 +190,51 @@ class GraphedStep:
         return self.out          # the graph's STATIC output buffer: the next replay overwrites it (clone to keep it)
 
 
+def retime_items(items, tempo, device, max_frames_per_batch=32768):
+    """Copies of `items` with "mel2ph" (and "f0", when present) retimed by the item's "ph_stretch" / its tempo (timing.retime), computed on the device in
+    collated groups and read back; the copies carry no "ph_stretch".  tempo: None, a number, or one number per item, finite and > 0 (ValueError);
+    "ph_stretch": one finite factor > 0 per token of the item (ValueError)."""
+    n = len(items)
+    tempos = [1.0] * n if tempo is None else timing.factor_tensor(tempo, n, "cpu").tolist()
+    stretches = []
+    for i, it in enumerate(items):
+        st = it.get("ph_stretch")
+        st = np.ones(len(it["text_tokens"]), np.float32) if st is None else np.asarray(st, dtype=np.float32)
+        if st.shape != (len(it["text_tokens"]),):
+            raise ValueError(f"item {i}: ph_stretch has shape {st.shape} for {len(it['text_tokens'])} tokens (one factor per token)")
+        if not (np.isfinite(st).all() and (st > 0).all()):
+            raise ValueError(f"item {i}: a stretch factor must be a finite number > 0")
+        if it.get("f0") is not None and np.shape(it["f0"]) != (len(it["mel2ph"]),):
+            raise ValueError(f"item {i}: the guide curve has {np.shape(it['f0'])} values for {len(it['mel2ph'])} frames (one value in Hz per frame)")
+        stretches.append(st)
+    out = [None] * n
+    guided = [it.get("f0") is not None for it in items]
+    for idx in bucket_by_length([len(it["mel2ph"]) for it in items], max_frames_per_batch, keys=guided):
+        B, T = len(idx), max(1, max(len(items[i]["mel2ph"]) for i in idx))
+        T_ph = max(len(items[i]["text_tokens"]) for i in idx)
+        m2p, st = torch.zeros((B, T), dtype=torch.long), torch.ones((B, T_ph), dtype=torch.float32)
+        curve = torch.zeros((B, T), dtype=torch.float32) if guided[idx[0]] else None
+        for b, i in enumerate(idx):
+            m2p[b, :len(items[i]["mel2ph"])] = torch.as_tensor(np.asarray(items[i]["mel2ph"]), dtype=torch.long)
+            st[b, :len(stretches[i])] = torch.from_numpy(stretches[i])
+            if curve is not None:
+                curve[b, :len(items[i]["f0"])] = torch.as_tensor(np.asarray(items[i]["f0"], dtype=np.float32))
+        new, lens, warped = timing.retime(mel2ph=m2p.to(device), T_ph=T_ph, stretch=st.to(device), tempo=[tempos[i] for i in idx],
+                                          curve=None if curve is None else curve.to(device))
+        new, lens = new.cpu().numpy(), lens.cpu().tolist()
+        warped = None if warped is None else warped.cpu().numpy()
+        for b, i in enumerate(idx):
+            out[i] = {k: v for k, v in items[i].items() if k != "ph_stretch"}
+            out[i]["mel2ph"] = new[b, :lens[b]].copy()
+            if warped is not None:
+                out[i]["f0"] = warped[b, :lens[b]].copy()
+    return out
+
+
 @torch.no_grad()
 def synthesize(model, items, hop_size, max_frames_per_batch=32768, noise_scale=1.0, generator=None, equal_tokens=False,
-               graphs=None, streams=2, seeds=None, takes=1, first_take=0, voicing="guide", pitch_shift_cents=None, return_f0=False):
+               graphs=None, streams=2, seeds=None, takes=1, first_take=0, voicing="guide", pitch_shift_cents=None, return_f0=False,
+               tempo=None):
     """Run VISinger.forward(infer=True) over length-bucketed batches.  Returns a list of float32 waveforms trimmed to
     each item's own length (frames * hop_size), in the input order.
 
@@ -205,7 +267,14 @@ def synthesize(model, items, hop_size, max_frames_per_batch=32768, noise_scale=1
     its mel2ph, 0 = unvoiced -- is sung on that guide; voicing="guide" takes the voiced frames from it, "model" keeps the predictor's own decision over the
     gap-interpolated guide.  Items with and without a guide never share a batch.  pitch_shift_cents: a number, or one per item in input order; transposes the
     conditioning curve (guide or predicted), read on the device.  return_f0: the result is a list of (wav, f0_hz) with f0_hz the float32 curve the prior was
-    conditioned on, in Hz (0 = unvoiced), trimmed to the item's frames.  Items without "f0" in a call without these arguments run exactly as before."""
+    conditioned on, in Hz (0 = unvoiced), trimmed to the item's frames.  Items without "f0" in a call without these arguments run exactly as before.
+
+    Tempo control (timing.retime): tempo -- a number, or one per item in input order, > 0 -- and an item's "ph_stretch" -- one factor > 0 per token -- retime
+    the item's mel2ph by ph_stretch[i] / tempo per token, and warp its "f0" with it, on the device in a pre-pass (retime_items); the call then runs on
+    copies of the items that carry the retimed alignment, so buckets, `ragged`, graphs and trimming see the new lengths.  The caller's items are not
+    modified.  Without tempo and without an item that carries "ph_stretch" there is no pre-pass."""
+    if tempo is not None or any(it.get("ph_stretch") is not None for it in items):
+        items = retime_items(items, tempo, next(model.parameters()).device, max_frames_per_batch)
     if voicing not in ("guide", "model"):
         raise ValueError(f"voicing must be 'guide' or 'model', got {voicing!r}")
     if pitch_shift_cents is not None:
