@@ -3,7 +3,9 @@
 // workgroups per CU.  Reports TFLOP/s by wall clock and the shader clock the loop ran at (s_memtime / s_memrealtime).
 // Measured (MI355X, this pool): 32x32x16 1.56-1.57 PFLOP/s at 1.66-1.67 GHz, 31.4 cycles per MFMA and SIMD -- the pipe is saturated
 // and the clock is what the power limit leaves of 2.4 GHz: the PRACTICAL ceiling of a bf16 MFMA kernel here is 0.63 of the spec
-// peak.  (The 16x16x32 arm keeps the six-deep dependent chains, which that shape does not issue back to back: not a fair rate.)
+// peak.  The 16x16x32 arm runs six K = 32 products on each of its 32 tiles: 192 MFMAs of 16384 FLOP = 96 x 32768 FLOP per iteration, TWICE the 32x32x16 arm's
+// 48 x 32768 -- each arm is charged its own count below (until round 7 both were charged 48, which halved this arm's figure; tools/ubench/mfma_shape_rate.hip,
+// profiles/r07_mfma_shape_rate.txt: ~2.0 PFLOP/s at 1.98 GHz with the pipe full, against 1.58 at 1.69 for 32x32x16).
 //   hipcc --offload-arch=gfx950 -O3 tools/ubench/mfma_bf16_rate.hip -o tools/ubench/mfma_bf16_rate && tools/ubench/mfma_bf16_rate
 #include <hip/hip_runtime.h>
 #include <cstdio>
@@ -50,7 +52,7 @@ __global__ void __launch_bounds__(256, 2) k(const u32x4 *in, float *out, unsigne
 #pragma unroll
             for (int j = 0; j < 32; ++j) {
 #pragma unroll
-                for (int t = 0; t < 6; ++t)     // 16x16x32 has half the FLOPs of 32x32x16: 32 tiles x 6 = the same work per iteration
+                for (int t = 0; t < 6; ++t)     // 16x16x32 has half the FLOPs of 32x32x16 and a quarter of its outputs: 32 tiles x 6 = 192 MFMAs = TWICE the work per iteration
                     acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a[t % 3]), __builtin_bit_cast(bf16x8, b[(t + j) % 3]), acc[j], 0, 0, 0);
             }
         }
@@ -81,9 +83,10 @@ static void run(const char *name, const u32x4 *in, float *out, unsigned long lon
     hipMemcpy(h.data(), clk, sizeof(unsigned long long) * 2 * blocks, hipMemcpyDeviceToHost);
     double cyc = 0, rt = 0;
     for (int i = 0; i < blocks; ++i) { cyc += h[2 * i]; rt += h[2 * i + 1]; }
-    const double flop = (double)reps * blocks * 4 /*waves*/ * iters * 48.0 * 32768.0;   // 48 MFMAs of 32x32x16 (or 96 x 2 of 16x16x32... 192 x half)
+    const double units = SHAPE == 0 ? 48.0 : 96.0;      // 32768-FLOP units per iteration and wave: 48 MFMAs of 32x32x16, 192 of 16x16x32 (16384 FLOP each)
+    const double flop = (double)reps * blocks * 4 /*waves*/ * iters * units * 32768.0;
     printf("%-10s  %8.1f TFLOP/s   shader clock %.3f GHz   %.1f cycles per 32768-FLOP MFMA-equivalent per wave\n", name,
-           flop / (ms * 1e-3) / 1e12, cyc / rt * 0.1, cyc / blocks / ((double)iters * 48.0));
+           flop / (ms * 1e-3) / 1e12, cyc / rt * 0.1, cyc / blocks / ((double)iters * units));
 }
 
 int main() {

@@ -9,15 +9,19 @@
 //   * a workgroup owns BN = 256 columns of the sequence and ALL channels.  The same BN columns go through every conv; each conv eats
 //     its receptive half-width off both ends of the range that is still exact, so after the block BN - 2 H columns are final outputs
 //     (H = the sum of the pads: 12 at k = 3, 36 at k = 7) and neighbouring tiles overlap by 2 H columns (recomputed, not exchanged);
-//   * the residual stream x lives in REGISTERS, fp32, in the accumulator layout of the 32x32 MFMA tile (row = (r&3) + 8(r>>2) + 4(lane>>5),
-//     column = lane&31): `x = xt + x` is an add on the accumulators of conv2, no LDS or HBM round trip, full fp32 precision;
+//   * the residual stream x lives in REGISTERS, fp32, in the accumulator layout of the MFMA tile: `x = xt + x` is an add on the accumulators of conv2, no
+//     LDS or HBM round trip, full fp32 precision.  A wave owns 32 rows x 32 NT_W columns.  The split-f16 kernels tile them with v_mfma_f32_16x16x32_f16
+//     (2 row tiles x 2 NT_W column tiles of four registers: row = 16 rt + 4(lane>>4) + r, column = 16 ct + (lane&15)); the chip holds a higher clock on that
+//     shape than on 32x32x16 at the same cycles per FLOP (tools/ubench/mfma_shape_rate.hip, profiles/r07_*).  -DVS_RB_MFMA32 (tools/build_variant.py) and the
+//     plain-bf16 kernel keep the 32x32x16 tiling (NT_W tiles of sixteen registers: row = (r&3) + 8(r>>2) + 4(lane>>5), column = lane&31);
 //   * the B operand of every conv is one LDS tile [plane(2)][channel group of 8][column + margin][8 f16], written straight from that
 //     layout (a lane holds 4 consecutive channels of a column = half a 16-byte cell: one ds_write_b64 per plane) after leaky-relu,
 //     zeroing outside the sequence (each conv's own zero padding) and the split x * s = xh + xl.  s is the power of two that puts
 //     the tile's largest magnitude below 2^15: one exponent per wave through LDS, merged behind the barrier that also ends the
 //     previous conv's reads of the tile;
 //   * every conv then is the barrier-free loop of resblock_pair_split.hip's phase 2: weight fragments from L2 one step ahead, each tap a
-//     shifted window of the tile, three f16 MFMAs per 16 channels and 32x32 outputs;
+//     shifted window of the tile, three f16 MFMAs per 32 channels and 16x16 outputs (per 16 channels and 32x32 outputs on the old shape).  The weight
+//     fragments are the pack's 16-byte cells under another lane map, the tile layout is the same for both shapes;
 //   * epilogue: the exact columns through the LDS transposition, float4 stores, the accumulate input read next to them.
 //
 // HBM traffic per block: x in, y out (+ acc in) for SIX convs; the 1-launch-per-conv form moves x, residual and y per conv.
@@ -33,6 +37,14 @@ __device__ __forceinline__ unsigned max3_u32(unsigned a, unsigned b, unsigned c)
     asm("v_max3_u32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
     return r;
 }
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+#ifdef VS_RB_MFMA32      // (the A/B library of tools/build_variant.py: every instance on the 32x32x16 shape)
+constexpr bool RB_MFMA16 = false;
+#else
+constexpr bool RB_MFMA16 = true;
+#endif
 
 constexpr int RB_MAXCONV = 6;
 constexpr int RB_MAXPAD = 28;      // largest pad of a conv of the chain: (k - 1) * d / 2 = 25 at k = 11, d = 5
@@ -89,14 +101,26 @@ __device__ __forceinline__ void resblock_body(const ResblockParams &p) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave % WAVES_M, wn = wave / WAVES_M;
-    const int lhalf = lane >> 5, l31 = lane & 31;
+    // M16: 16x16x32 MFMAs.  A tile `a` of the wave's 32 x 32 NT_W outputs is (column tile a >> 1 of 16, row tile a & 1 of 16) in four registers,
+    // on the old shape column tile a of 32 in sixteen; tile_col / tile_row are a lane's column and rows within the wave's range either way.
+    constexpr bool M16 = RB_MFMA16 && PLANES == 2;
+    constexpr int NA = M16 ? 4 * NT_W : NT_W, AR = M16 ? 4 : 16;      // tiles per wave, registers per tile
+    constexpr int NCT = M16 ? 2 * NT_W : NT_W, CTW = M16 ? 16 : 32;   // column tiles and their width
+    constexpr int RT = M16 ? 2 : 1;                                   // row tiles = weight fragments per plane and step
+    constexpr int KSTEP = M16 ? 32 : 16;                              // channels per step
+    using acc_t = std::conditional_t<M16, f32x4, f32x16>;
+    auto ct_of = [](int a) { return M16 ? (a >> 1) : a; };
+    const int lhalf = lane >> 5;
+    const int lcol = lane & (CTW - 1);
+    auto tile_col = [&](int a) { return ct_of(a) * CTW + lcol; };
     const int b = blockIdx.z;
     const int NOUT = BN - 2 * p.H;
     const int n0 = blockIdx.x * NOUT;              // first final output of this tile
     const int t0 = n0 - p.H;                       // sequence position of tile column 0
     const int KT = p.K;
-    const int nsteps = p.nchunks * KT;
-    auto acc_row = [&](int r) { return (r & 3) + 8 * (r >> 2) + 4 * lhalf; };
+    const int nch = p.nchunks / (KSTEP / 16);      // (p.nchunks counts the pack's 16-channel chunks; C is a multiple of 32)
+    const int nsteps = nch * KT;
+    auto tile_row = [&](int a, int r) { return M16 ? 16 * (a & 1) + 4 * (lane >> 4) + r : (r & 3) + 8 * (r >> 2) + 4 * lhalf; };
 
     rb_stamp(p, 0);
     // margins of the tile: zeros, once (the waves only ever write their own BN columns)
@@ -106,61 +130,78 @@ __device__ __forceinline__ void resblock_body(const ResblockParams &p) {
     }
 
     // ---- the residual stream: x in the accumulator layout, zero outside the sequence
-    bool inside[NT_W];
-    f32x16 xr[NT_W], acc[NT_W];
+    bool inside[NCT];
+    acc_t xr[NA], acc[NA];
     {
         const char *const xbase = reinterpret_cast<const char *>(p.x) + (long long)b * p.x_bs * (PB ? 2 : 4);
         const __amdgpu_buffer_rsrc_t xsrc =
             __builtin_amdgcn_make_buffer_rsrc((void *)xbase, 0, (int)((long long)p.C * p.T * (PB ? 2 : 4)), 0x00020000);
 #pragma unroll
-        for (int j = 0; j < NT_W; ++j) {
-            const int n = t0 + wn * (NT_W * 32) + j * 32 + l31;
+        for (int j = 0; j < NCT; ++j) {
+            const int n = t0 + wn * (NT_W * 32) + j * CTW + lcol;
             inside[j] = (n >= 0) && (n < p.T);
-            const int nc = min(max(n, 0), p.T - 1);
+        }
 #pragma unroll
-            for (int r = 0; r < 16; ++r) {
+        for (int a = 0; a < NA; ++a) {
+            const int nc = min(max(t0 + wn * (NT_W * 32) + tile_col(a), 0), p.T - 1);
+#pragma unroll
+            for (int r = 0; r < AR; ++r) {
                 if constexpr (PB)
-                    xr[j][r] = u2f((unsigned)(unsigned short)__builtin_amdgcn_raw_buffer_load_b16(xsrc, ((wm * 32 + acc_row(r)) * p.T + nc) * 2, 0, 0) << 16);
+                    xr[a][r] = u2f((unsigned)(unsigned short)__builtin_amdgcn_raw_buffer_load_b16(xsrc, ((wm * 32 + tile_row(a, r)) * p.T + nc) * 2, 0, 0) << 16);
                 else
-                    xr[j][r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(xsrc, ((wm * 32 + acc_row(r)) * p.T + nc) * 4, 0, 0));
+                    xr[a][r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(xsrc, ((wm * 32 + tile_row(a, r)) * p.T + nc) * 4, 0, 0));
             }
         }
 #pragma unroll
-        for (int j = 0; j < NT_W; ++j)
+        for (int a = 0; a < NA; ++a)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) xr[j][r] = inside[j] ? xr[j][r] : 0.f;
+            for (int r = 0; r < AR; ++r) xr[a][r] = inside[ct_of(a)] ? xr[a][r] : 0.f;
     }
 
     // (wave-uniform: every column of this wave's tiles lies inside the sequence)
     bool all_in = true;
 #pragma unroll
-    for (int j = 0; j < NT_W; ++j) all_in = all_in && (__builtin_amdgcn_ballot_w64(inside[j]) == ~0ull);
+    for (int j = 0; j < NCT; ++j) all_in = all_in && (__builtin_amdgcn_ballot_w64(inside[j]) == ~0ull);
     rb_stamp(p, 1);
-    // one (chunk, tap) step: NT_W column tiles x 3 cross products; the planes of tile j+1 are read under the MFMAs of tile j
+    // one (chunk, tap) step: NCT column tiles x RT row tiles x 3 cross products; the planes of column tile j+1 are read under the MFMAs of tile j
+    // (16x16x32: the two row tiles of a column tile take each product in turn, so no MFMA follows one on its own accumulator)
     // ZC: the first step of a conv -- the first product of every column tile takes a ZERO C operand (an inline constant of the instruction) instead of the
     // accumulators being cleared by 64 moves per conv beforehand
-    auto mma_step = [&](const u32x4 (&acur)[PLANES], const unsigned *xs, auto zc_c) __attribute__((always_inline)) {
+    auto mma_step = [&](const u32x4 (&acur)[RT][PLANES], const unsigned *xs, auto zc_c) __attribute__((always_inline)) {
         constexpr bool ZC = decltype(zc_c)::value;
         const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
         u32x4 bf[PLANES], bn[PLANES];
 #pragma unroll
         for (int pl = 0; pl < PLANES; ++pl) bf[pl] = *reinterpret_cast<const u32x4 *>(xs + pl * TPL);
 #pragma unroll
-        for (int j = 0; j < NT_W; ++j) {
-            if (j + 1 < NT_W) {
+        for (int j = 0; j < NCT; ++j) {
+            if (j + 1 < NCT) {
 #pragma unroll
-                for (int pl = 0; pl < PLANES; ++pl) bn[pl] = *reinterpret_cast<const u32x4 *>(xs + pl * TPL + (j + 1) * 128);
+                for (int pl = 0; pl < PLANES; ++pl) bn[pl] = *reinterpret_cast<const u32x4 *>(xs + pl * TPL + (j + 1) * (CTW * 4));
             }
             __builtin_amdgcn_sched_barrier(0);
-            if constexpr (PLANES == 2) {
+            if constexpr (M16) {
                 auto mm = [&](int ta, int tb) __attribute__((always_inline)) {
-                    acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, acur[ta]), __builtin_bit_cast(f16x8, bf[tb]), acc[j], 0, 0, 0);
+#pragma unroll
+                    for (int rt = 0; rt < 2; ++rt)
+                        acc[2 * j + rt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, acur[rt][ta]), __builtin_bit_cast(f16x8, bf[tb]), acc[2 * j + rt], 0, 0, 0);
                 };
-                if constexpr (ZC) acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, acur[1]), __builtin_bit_cast(f16x8, bf[0]), zero16, 0, 0, 0);
+                if constexpr (ZC) {
+#pragma unroll
+                    for (int rt = 0; rt < 2; ++rt)
+                        acc[2 * j + rt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, acur[rt][1]), __builtin_bit_cast(f16x8, bf[0]), zero4, 0, 0, 0);
+                } else mm(1, 0);
+                mm(0, 1); mm(0, 0);        // smallest terms first
+            } else if constexpr (PLANES == 2) {
+                auto mm = [&](int ta, int tb) __attribute__((always_inline)) {
+                    acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, acur[0][ta]), __builtin_bit_cast(f16x8, bf[tb]), acc[j], 0, 0, 0);
+                };
+                if constexpr (ZC) acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, acur[0][1]), __builtin_bit_cast(f16x8, bf[0]), zero16, 0, 0, 0);
                 else mm(1, 0);
                 mm(0, 1); mm(0, 0);        // smallest terms first
             } else {
-                acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, acur[0]), __builtin_bit_cast(bf16x8, bf[0]), ZC ? zero16 : acc[j], 0, 0, 0);
+                acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, acur[0][0]), __builtin_bit_cast(bf16x8, bf[0]), ZC ? zero16 : acc[j], 0, 0, 0);
             }
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -174,7 +215,7 @@ __device__ __forceinline__ void resblock_body(const ResblockParams &p) {
         //  loop-invariant registers they were spilled and reloaded once per conv)
         int lane_c = lane;
         asm volatile("" : "+v"(lane_c));
-        const int lh = lane_c >> 5, l5 = lane_c & 31;
+        const int lh = lane_c >> 5, l5 = lane_c & (CTW - 1);
         // ---- this conv's input in the accumulator registers: lrelu(x) (first conv of a pair) or lrelu(conv1 + b1) (second), zero outside
         unsigned mkey = 0u;
         // (0.1 v for two values per instruction: v_pk_mul_f32 on the register pairs of the accumulator tile)
@@ -185,13 +226,13 @@ __device__ __forceinline__ void resblock_body(const ResblockParams &p) {
         auto transform = [&](auto in_c) __attribute__((always_inline)) {
             constexpr bool ALL_IN = decltype(in_c)::value;
 #pragma unroll
-            for (int j = 0; j < NT_W; ++j)
+            for (int j = 0; j < NA; ++j)
 #pragma unroll
-                for (int r = 0; r < 16; r += 2) {
+                for (int r = 0; r < AR; r += 2) {
                     const f32x2 v2 = second ? f32x2{acc[j][r], acc[j][r + 1]} : f32x2{xr[j][r], xr[j][r + 1]};
                     const f32x2 t2 = v2 * slope2;
                     float v0 = fmaxf(v2.x, t2.x), v1 = fmaxf(v2.y, t2.y);
-                    if constexpr (!ALL_IN) { v0 = inside[j] ? v0 : 0.f; v1 = inside[j] ? v1 : 0.f; }
+                    if constexpr (!ALL_IN) { v0 = inside[ct_of(j)] ? v0 : 0.f; v1 = inside[ct_of(j)] ? v1 : 0.f; }
                     acc[j][r] = v0;
                     acc[j][r + 1] = v1;
                     if constexpr (PLANES == 2) mkey = max3_u32(mkey, (f2u(v0) << 1) + 0x01000000u, (f2u(v1) << 1) + 0x01000000u);      // (f16_maxkey of both)
@@ -215,11 +256,13 @@ __device__ __forceinline__ void resblock_body(const ResblockParams &p) {
         }
         rb_stamp(p, 2 + 4 * c);
         // ---- split and write the tile
+        // (a lane's four consecutive registers are four consecutive channels of its column either way: 16x16x32, tile (ct, rt): channel group 2 rt + (lane >> 5),
+        //  half (lane >> 4) & 1 of the cell; 32x32x16, registers 4 g ...: group g, half lane >> 5)
 #pragma unroll
-        for (int j = 0; j < NT_W; ++j) {
-            const int col = MP + wn * (NT_W * 32) + j * 32 + l5;
+        for (int j = 0; j < NA; ++j) {
+            const int col = MP + wn * (NT_W * 32) + ct_of(j) * CTW + l5;
 #pragma unroll
-            for (int g = 0; g < 4; ++g) {
+            for (int g = 0; g < AR / 4; ++g) {
                 unsigned d0[PLANES], d1[PLANES];
                 if constexpr (PLANES == 2) {
                     const f32x2 sx2 = {sx, sx};
@@ -230,7 +273,7 @@ __device__ __forceinline__ void resblock_body(const ResblockParams &p) {
                     split_pair<1>(acc[j][4 * g], acc[j][4 * g + 1], d0);
                     split_pair<1>(acc[j][4 * g + 2], acc[j][4 * g + 3], d1);
                 }
-                unsigned *dst = Tb + ((wm * 4 + g) * WT + col) * 4 + lh * 2;
+                unsigned *dst = M16 ? Tb + ((wm * 4 + 2 * (j & 1) + lh) * WT + col) * 4 + ((lane_c >> 4) & 1) * 2 : Tb + ((wm * 4 + g) * WT + col) * 4 + lh * 2;
 #pragma unroll
                 for (int pl = 0; pl < PLANES; ++pl) *reinterpret_cast<uint2 *>(dst + pl * TPL) = make_uint2(d0[pl], d1[pl]);
             }
@@ -238,27 +281,32 @@ __device__ __forceinline__ void resblock_body(const ResblockParams &p) {
         // ---- weight fragments of the first step, then the conv (the accumulators are cleared by the first step's zero C operand)
         const int d = p.dil[c];
         const int pad = d * (KT - 1) / 2;
-        const u32x4 *const wbase = reinterpret_cast<const u32x4 *>(p.ws[c]) + (long long)wm * KT * p.nchunks * (PLANES * 64) + lane_c;
-        u32x4 a0[PLANES], a1[PLANES];
+        // (16x16x32: the fragment of row tile rt and 32-channel chunk C holds, for lane (r16, g = K group of 8), the pack's cell of 16-channel chunk 2 C + (g >> 1),
+        //  lane 16 rt + r16 + 32 (g & 1): the same 16-byte loads under another lane map, two per plane and 32 channels as before)
+        const int lane_w = M16 ? (lane_c >> 5) * (PLANES * 64) + (lane_c & 15) + 32 * ((lane_c >> 4) & 1) : lane_c;
+        const u32x4 *const wbase = reinterpret_cast<const u32x4 *>(p.ws[c]) + (long long)wm * KT * p.nchunks * (PLANES * 64) + lane_w;
+        u32x4 a0[RT][PLANES], a1[RT][PLANES];
         // (fragment and tile positions as RUNNING offsets -- one scalar add per step each where (tap * nchunks + chunk) * (PLANES * 64) was a 64-bit multiply
         //  and the tile address a v_mul_lo: the scalar stream of a step is what it costs next to its 4-12 MFMAs)
-        const int a_dtap = p.nchunks * (PLANES * 64), a_dwrap = (PLANES * 64) - (KT - 1) * a_dtap;
-        const int a_last = ((KT - 1) * p.nchunks + (p.nchunks - 1)) * (PLANES * 64);
+        const int a_dtap = p.nchunks * (PLANES * 64), a_dwrap = (KSTEP / 16) * (PLANES * 64) - (KT - 1) * a_dtap;
+        const int a_last = ((KT - 1) * p.nchunks + (p.nchunks - KSTEP / 16)) * (PLANES * 64);
         int aoff = 0;
-        auto load_a = [&](u32x4 (&dst)[PLANES]) __attribute__((always_inline)) {
+        auto load_a = [&](u32x4 (&dst)[RT][PLANES]) __attribute__((always_inline)) {
             const u32x4 *src = wbase + min(aoff, a_last);          // (clamped: the last step's extra request, never used, stays inside this conv's fragments)
 #pragma unroll
-            for (int pl = 0; pl < PLANES; ++pl) dst[pl] = src[pl * 64];
+            for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+                for (int pl = 0; pl < PLANES; ++pl) dst[rt][pl] = src[pl * 64 + rt * 16];
         };
         int pt = 0, tap = 0, s = 0;
         auto advance = [&]() __attribute__((always_inline)) { if (++pt == KT) { pt = 0; aoff += a_dwrap; } else aoff += a_dtap; };
         load_a(a0); advance();
         __syncthreads();
         rb_stamp(p, 3 + 4 * c);
-        const unsigned *const xlane = Tb + (lh * WT + MP + wn * (NT_W * 32) + l5 - pad) * 4;
-        const int x_dtap = d * 4, x_dwrap = 2 * WT * 4 - (KT - 1) * d * 4;
+        const unsigned *const xlane = Tb + ((M16 ? lane_c >> 4 : lh) * WT + MP + wn * (NT_W * 32) + l5 - pad) * 4;      // (the B fragment: K group of 8 channels, column)
+        const int x_dtap = d * 4, x_dwrap = (KSTEP / 8) * WT * 4 - (KT - 1) * d * 4;
         int xoff = 0;
-        auto step = [&](u32x4 (&acur)[PLANES], u32x4 (&apre)[PLANES], auto zc_c) __attribute__((always_inline)) {
+        auto step = [&](u32x4 (&acur)[RT][PLANES], u32x4 (&apre)[RT][PLANES], auto zc_c) __attribute__((always_inline)) {
             // (UNCONDITIONAL: behind `if (s + 1 < nsteps)` hipcc's wait in front of this step's first MFMA was vmcnt(0) -- the scoreboard merge of the two
             //  paths -- which also waited for the fragments requested on the line above: one exposed L2 round trip per step pair in every conv of
             //  every fused block.  Round 4, found in the ISA.)
@@ -267,7 +315,7 @@ __device__ __forceinline__ void resblock_body(const ResblockParams &p) {
             if (++tap == KT) { tap = 0; xoff += x_dwrap; } else xoff += x_dtap;
             ++s;
         };
-        step(a0, a1, std::true_type{});                      // (nsteps >= 2: two chunks at 32 channels, three taps at least)
+        step(a0, a1, std::true_type{});                      // (nsteps >= 2: three taps at least)
         step(a1, a0, std::false_type{});
         while (s < nsteps) {
             step(a0, a1, std::false_type{});
@@ -279,31 +327,37 @@ __device__ __forceinline__ void resblock_body(const ResblockParams &p) {
         const float *const bias = p.bias[c] + wm * 32;
         // (two values per instruction: v_pk_mul_f32 / v_pk_fma_f32 / v_pk_add_f32 on the register pairs (r, r + 1) of an accumulator tile)
         const f32x2 isx2 = {isx, isx}, isw2 = {isw, isw};
+        // (the row of register r of the tiles of row tile rt, from this conv's opaque lane id: tile_row's map)
+        auto brow = [&](int rt, int r) { return M16 ? 16 * rt + 4 * (lane_c >> 4) + r : (r & 3) + 8 * (r >> 2) + 4 * lh; };
         // (`second` is wave-uniform: a branch around each form -- as selects inside one loop the update cost two v_cndmask per value)
         if (second) {
 #pragma unroll
-            for (int r = 0; r < 16; r += 2) {
-                const f32x2 bv2 = {bias[(r & 3) + 8 * (r >> 2) + 4 * lh], bias[((r + 1) & 3) + 8 * ((r + 1) >> 2) + 4 * lh]};
+            for (int rt = 0; rt < RT; ++rt)
 #pragma unroll
-                for (int j = 0; j < NT_W; ++j) {
-                    const f32x2 a = {acc[j][r], acc[j][r + 1]};
-                    const f32x2 v = __builtin_elementwise_fma(a * isx2, isw2, bv2);
-                    f32x2 x2 = {xr[j][r], xr[j][r + 1]};
-                    x2 += v;
-                    xr[j][r] = x2.x; xr[j][r + 1] = x2.y;
+                for (int r = 0; r < AR; r += 2) {
+                    const f32x2 bv2 = {bias[brow(rt, r)], bias[brow(rt, r + 1)]};
+#pragma unroll
+                    for (int j = rt; j < NA; j += RT) {
+                        const f32x2 a = {acc[j][r], acc[j][r + 1]};
+                        const f32x2 v = __builtin_elementwise_fma(a * isx2, isw2, bv2);
+                        f32x2 x2 = {xr[j][r], xr[j][r + 1]};
+                        x2 += v;
+                        xr[j][r] = x2.x; xr[j][r + 1] = x2.y;
+                    }
                 }
-            }
         } else {
 #pragma unroll
-            for (int r = 0; r < 16; r += 2) {
-                const f32x2 bv2 = {bias[(r & 3) + 8 * (r >> 2) + 4 * lh], bias[((r + 1) & 3) + 8 * ((r + 1) >> 2) + 4 * lh]};
+            for (int rt = 0; rt < RT; ++rt)
 #pragma unroll
-                for (int j = 0; j < NT_W; ++j) {
-                    const f32x2 a = {acc[j][r], acc[j][r + 1]};
-                    const f32x2 v = __builtin_elementwise_fma(a * isx2, isw2, bv2);
-                    acc[j][r] = v.x; acc[j][r + 1] = v.y;
+                for (int r = 0; r < AR; r += 2) {
+                    const f32x2 bv2 = {bias[brow(rt, r)], bias[brow(rt, r + 1)]};
+#pragma unroll
+                    for (int j = rt; j < NA; j += RT) {
+                        const f32x2 a = {acc[j][r], acc[j][r + 1]};
+                        const f32x2 v = __builtin_elementwise_fma(a * isx2, isw2, bv2);
+                        acc[j][r] = v.x; acc[j][r + 1] = v.y;
+                    }
                 }
-            }
         }
         rb_stamp(p, 5 + 4 * c);
     }
@@ -319,49 +373,54 @@ __device__ __forceinline__ void resblock_body(const ResblockParams &p) {
     unsigned short *const yh = reinterpret_cast<unsigned short *>(p.y) + (long long)b * p.y_bs;                 // PB: bf16 elements
     const unsigned short *const acch = reinterpret_cast<const unsigned short *>(p.acc) + (long long)b * p.acc_bs;
     if (p.fast_epi && (n0 + NOUT <= p.T)) {
-        constexpr int CW = 32 * NT_W, LPR = CW / 4, RPI = 64 / LPR, NIT = 8 / RPI;
-        float *const Lw = smem + wave * 8 * CW;
+        // (a pass transposes the rows one register index of every tile covers at once: 16 on the 16x16 tiles -- 4 (lane >> 4) + q of row tile ps --, 8 on the
+        //  32x32 tiles -- q + 4 (lane >> 5) of row block ps)
+        constexpr int CW = 32 * NT_W, LPR = CW / 4, RPI = 64 / LPR, RPP = M16 ? 16 : 8, NPS = 32 / RPP, NIT = RPP / RPI;
+        float *const Lw = smem + wave * RPP * CW;
         const int lrow = lane_e / LPR, c4 = (lane_e % LPR) * 4;
         const int ctile = wn * CW + c4;                          // column within the tile
         const bool live = (ctile >= p.H) && (ctile < BN - p.H);  // H % 4 == 0: a float4 is all in or all out
         const long long goff0 = (long long)(tile_row0 + lrow) * p.T + t0 + ctile;
-        float4 a4[4][NIT];
+        float4 a4[NPS][NIT];
         if (live && has_acc) {
 #pragma unroll
-            for (int ps = 0; ps < 4; ++ps)
+            for (int ps = 0; ps < NPS; ++ps)
 #pragma unroll
                 for (int it = 0; it < NIT; ++it) {
-                    if constexpr (PB) a4[ps][it] = bf4_to_f4(*reinterpret_cast<const uint2 *>(acch + goff0 + (long long)(8 * ps + it * RPI) * p.T));
-                    else a4[ps][it] = *reinterpret_cast<const float4 *>(accp + goff0 + (long long)(8 * ps + it * RPI) * p.T);
+                    if constexpr (PB) a4[ps][it] = bf4_to_f4(*reinterpret_cast<const uint2 *>(acch + goff0 + (long long)(RPP * ps + it * RPI) * p.T));
+                    else a4[ps][it] = *reinterpret_cast<const float4 *>(accp + goff0 + (long long)(RPP * ps + it * RPI) * p.T);
                 }
         }
 #pragma unroll
-        for (int ps = 0; ps < 4; ++ps) {
+        for (int ps = 0; ps < NPS; ++ps) {
 #pragma unroll
             for (int q = 0; q < 4; ++q)
 #pragma unroll
-                for (int j = 0; j < NT_W; ++j) Lw[(q + 4 * (lane_e >> 5)) * CW + 32 * j + (lane_e & 31)] = xr[j][4 * ps + q];
+                for (int j = 0; j < NCT; ++j) {
+                    if constexpr (M16) Lw[(q + 4 * (lane_e >> 4)) * CW + 16 * j + (lane_e & 15)] = xr[2 * j + ps][q];
+                    else Lw[(q + 4 * (lane_e >> 5)) * CW + 32 * j + (lane_e & 31)] = xr[j][4 * ps + q];
+                }
             if (live) {
 #pragma unroll
                 for (int it = 0; it < NIT; ++it) {
                     float4 v = *reinterpret_cast<const float4 *>(Lw + (it * RPI + lrow) * CW + c4);
                     if (has_acc) { v.x += a4[ps][it].x; v.y += a4[ps][it].y; v.z += a4[ps][it].z; v.w += a4[ps][it].w; }
                     if (p.scale != 1.f) { v.x *= p.scale; v.y *= p.scale; v.z *= p.scale; v.w *= p.scale; }
-                    if constexpr (PB) *reinterpret_cast<uint2 *>(yh + goff0 + (long long)(8 * ps + it * RPI) * p.T) = f4_to_bf4(v);
-                    else *reinterpret_cast<float4 *>(yb + goff0 + (long long)(8 * ps + it * RPI) * p.T) = v;
+                    if constexpr (PB) *reinterpret_cast<uint2 *>(yh + goff0 + (long long)(RPP * ps + it * RPI) * p.T) = f4_to_bf4(v);
+                    else *reinterpret_cast<float4 *>(yb + goff0 + (long long)(RPP * ps + it * RPI) * p.T) = v;
                 }
             }
         }
     } else {
 #pragma unroll
-        for (int j = 0; j < NT_W; ++j) {
-            const int ctile = wn * (NT_W * 32) + j * 32 + l31;
+        for (int j = 0; j < NA; ++j) {
+            const int ctile = wn * (NT_W * 32) + tile_col(j);
             const int n = t0 + ctile;
             const bool okc = (ctile >= p.H) && (ctile < BN - p.H) && (n < p.T);      // (n >= 0 on exact columns: t0 + H = n0 >= 0)
             const int nc = min(max(n, 0), p.T - 1);
 #pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const long long off = (long long)(tile_row0 + acc_row(r)) * p.T + nc;
+            for (int r = 0; r < AR; ++r) {
+                const long long off = (long long)(tile_row0 + tile_row(j, r)) * p.T + nc;
                 float v = xr[j][r];
                 if constexpr (PB) {
                     if (has_acc) v += u2f((unsigned)acch[off] << 16);
@@ -381,8 +440,9 @@ __device__ __forceinline__ void resblock_body(const ResblockParams &p) {
     }
 }
 
+// (NT_W = 2: the 256-column tile at 32 channels runs four workgroups per CU; the bound keeps the instance at the 128 registers that takes)
 template <int NT_W, int WAVES_M, int WAVES_N, int MP>
-__global__ void __launch_bounds__(64 * WAVES_M * WAVES_N, 2) resblock_f16_kernel(const ResblockParams p) {
+__global__ void __launch_bounds__(64 * WAVES_M * WAVES_N, NT_W == 2 ? 4 : 2) resblock_f16_kernel(const ResblockParams p) {
     resblock_body<NT_W, WAVES_M, WAVES_N, MP, 2, false>(p);
 }
 
@@ -397,7 +457,8 @@ static int margin_of(int maxpad) { return maxpad <= 8 ? 8 : (maxpad <= 16 ? 16 :
 template <int NT_W, int WAVES_M, int WAVES_N>
 static size_t resblock_lds(int MP, int planes = 2) {
     constexpr int BN = 32 * NT_W * WAVES_N, KG = 4 * WAVES_M;
-    return std::max<size_t>((size_t)planes * KG * (BN + 2 * MP) * 16 + 64, (size_t)WAVES_M * WAVES_N * 8 * (32 * NT_W) * sizeof(float));
+    // (the epilogue transposes 16 rows a pass per wave on the 16x16x32 shape, 8 on 32x32x16)
+    return std::max<size_t>((size_t)planes * KG * (BN + 2 * MP) * 16 + 64, (size_t)WAVES_M * WAVES_N * (RB_MFMA16 && planes == 2 ? 16 : 8) * (32 * NT_W) * sizeof(float));
 }
 
 template <int NT_W, int WAVES_M, int WAVES_N, int MP, bool BF>
