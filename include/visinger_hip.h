@@ -399,6 +399,32 @@ VS_API int vs_retime_frames(const int64_t *cum_old, const int64_t *cum_new, cons
                             int64_t *mel2ph_out, float *curve_out, int64_t B, int64_t T_tokens, int64_t T_out, void *stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * f6  pitch tracking (csrc/pitch_track.hip): the per-frame f0 curve of a batch of recordings, in the convention of f4 / f5 (Hz, 0 = unvoiced,
+ *     one value per hop).  Not in the reference (its extractors are parselmouth / pyworld on the host).  YIN (de Cheveigne & Kawahara 2002) with a LAG-CENTRED
+ *     difference function.  wav: fp32 [B, L]; lengths: DEVICE int64 [B] (clamped to [0, L]) or NULL = L; f0_hz, periodicity (or NULL): fp32 [B, T], T the caller's.
+ *       tau_max = ceil(sr / f0_min), tau_min = max(2, floor(sr / f0_max)) (in double), W = window, or 2 tau_max when window = 0;
+ *       n_b = min(lengths[b] / hop, T); frames t >= n_b: f0 = periodicity = 0; a sample at or beyond lengths[b], or before 0, reads as 0.
+ *     Frame t < n_b, c = t hop + hop / 2 (integer divisions throughout):
+ *       1. d(tau) = sum_{j = 0 .. W-1} (x[s + j] - x[s + j + tau])^2,  s = c - W/2 - tau/2,  tau = 1 .. tau_max + 1  (the direct form, never energy - 2 acf);
+ *       2. S(tau) = d(1) + .. + d(tau);  d'(tau) = d(tau) tau / S(tau) where 0 < S(tau) < inf, else 1 (a NaN or infinite sample in a lag's span: d' = 1 there);
+ *       3. g = argmin of d' over [tau_min, tau_max], the lowest tau on a tie;  periodicity = clamp(1 - d'(g), 0, 1);
+ *       4. e = sum_{j < W} x[c - W/2 + j]^2.  e not finite: f0 = 0 and periodicity = 0.  e <= silence * W (one fp32 product): f0 = 0.  Otherwise p = the first tau in
+ *          [tau_min, tau_max] with d'(tau) < threshold, then p <- p + 1 while p + 1 <= tau_max and d'(p + 1) < d'(p); no such tau: f0 = 0;
+ *       5. y0, y1, y2 = d'(p - 1), d'(p), d'(p + 1);  den = y0 - 2 y1 + y2;  off = den > 0 ? clamp(0.5 (y0 - y2) / den, -0.5, 0.5) : 0;  f0 = sr / (p + off).
+ *     fp32 throughout, in an order fixed per frame and lag -- a frame's outputs depend on the samples of its own span only, not on B, the row, L, T, the padding
+ *     or how many frames a workgroup takes:
+ *       d(tau) = ((B_0 + B_1) + B_2) + ..., B_k = the chain acc = fmaf(v, v, acc) from 0 over j = 32k .. min(32k + 31, W - 1) ascending, v = the rounded difference;
+ *       S(tau) = E_l + P, l = (tau - 1) / 17, P = d(17 l + 1) + .. + d(tau) ascending from 0, E_l = the sum of the chunk totals below l, formed over 64 chunks by
+ *                the doubling scan v_l += v_{l - s}, s = 1, 2, 4, .. 32 (chunks beyond tau_max + 1 count 0) and taken from chunk l - 1 (E_0 = 0);
+ *       e: partial l = the fmaf chain over j = l, l + 64, .. ascending, l < 64, then the butterfly e_l += e_{l ^ s}, s = 32, 16, .. 1;
+ *       d' = (d * float(tau)) / S, off and f0 as written, IEEE fp32 operations.
+ *     VS_EINVAL before anything is launched: NULL wav / f0_hz, aliased buffers, B, L, T <= 0, L >= 2^31 (or T), hop < 1, sr < 1, f0_min / f0_max / threshold not
+ *     finite and > 0, f0_min >= f0_max, tau_max > 1024, tau_min >= tau_max, W outside [tau_max, 2048], silence < 0 (or NaN).  One launch, no allocation, no atomics,
+ *     no host synchronisation; wav and lengths are read on the device: a captured graph replays on another recording by overwriting them.                    */
+VS_API int vs_f0_yin(const float *wav, const int64_t *lengths, int64_t B, int64_t L, int sr, int hop, float f0_min, float f0_max, int window,
+                     float threshold, float silence, float *f0_hz, float *periodicity, int64_t T, void *stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * a13 grouped / strided Conv1d of the scale discriminator (modules/discriminator.py:55-60) and its gradients.
  *     x: [B, c_in, T], w: [c_out, c_in/groups, k], y / gy: [B, c_out, T_out], T_out = (T + 2*pad - k)/stride + 1.
  *     vs_gconv1d_bwd_weight writes one plane per batch item, gw_planes [B][c_out, c_in/groups, k]; gw = their sum.

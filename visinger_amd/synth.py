@@ -5,7 +5,7 @@ int16).  Host-side plumbing only."""
 import numpy as np
 import torch
 
-from . import pitch, sampling, timing
+from . import pitch, pitch_track, sampling, timing
 
 
 def bucket_by_length(lengths, max_frames_per_batch, max_items_per_batch=256, keys=None):
@@ -190,6 +190,45 @@ class GraphedStep:
         return self.out          # the graph's STATIC output buffer: the next replay overwrites it (clone to keep it)
 
 
+def guide_items(items, hop_size, device, max_frames_per_batch=32768, **track):
+    """Copies of `items` in which a recording "guide_wav" -- a 1-D float array at the model's sample rate -- is replaced by "f0": its pitch curve, tracked on
+    the device (pitch_track.extract_f0(**track), which needs sample_rate) in length buckets -- zero-padded, the lengths in a device tensor -- read back and fitted
+    to the item's len(mel2ph): a longer curve is cut there, a shorter one padded with 0 (unvoiced: vs_f0_norm_interp bridges it like any gap).  Items without a
+    recording are passed on as they are.  ValueError: no sample_rate, an item with both "f0" and "guide_wav", a recording that is not 1-D or shorter than a hop."""
+    if "sample_rate" not in track:
+        raise ValueError("guide_track must contain sample_rate (the rate of the recordings, which is the model's)")
+    if set(track) - {"sample_rate", "f0_min", "f0_max", "window", "threshold", "silence"}:
+        raise ValueError(f"guide_track takes sample_rate, f0_min, f0_max, window, threshold and silence, got {sorted(track)}")
+    pitch_track.check_args(hop_size, **track)
+    wavs = {}
+    for i, it in enumerate(items):
+        if it.get("guide_wav") is None:
+            continue
+        if it.get("f0") is not None:
+            raise ValueError(f"item {i} carries both a guide curve ('f0') and a recording ('guide_wav'): give one of them")
+        w = np.asarray(it["guide_wav"])
+        if w.ndim != 1 or not np.issubdtype(w.dtype, np.floating) or len(w) < hop_size:
+            raise ValueError(f"item {i}: guide_wav must be a 1-D float array of at least hop_size = {hop_size} samples, got {w.dtype} {w.shape}")
+        wavs[i] = w.astype(np.float32, copy=False)
+    out = [dict(it) for it in items]
+    order = list(wavs)
+    for idx in bucket_by_length([len(wavs[i]) // hop_size for i in order], max_frames_per_batch):
+        idx = [order[j] for j in idx]
+        n = max(len(wavs[i]) for i in idx)
+        wav = torch.zeros((len(idx), n), dtype=torch.float32)
+        for b, i in enumerate(idx):
+            wav[b, :len(wavs[i])] = torch.from_numpy(wavs[i])
+        lens = torch.tensor([len(wavs[i]) for i in idx], dtype=torch.int64).to(device)
+        f0 = pitch_track.extract_f0(wav.to(device), hop_size, lengths=lens, **track).cpu().numpy()
+        for b, i in enumerate(idx):
+            T, have = len(items[i]["mel2ph"]), min(len(wavs[i]) // hop_size, len(items[i]["mel2ph"]))
+            curve = np.zeros(T, np.float32)
+            curve[:have] = f0[b, :have]
+            del out[i]["guide_wav"]
+            out[i]["f0"] = curve
+    return out
+
+
 def retime_items(items, tempo, device, max_frames_per_batch=32768):
     """Copies of `items` with "mel2ph" (and "f0", when present) retimed by the item's "ph_stretch" / its tempo (timing.retime), computed on the device in
     collated groups and read back; the copies carry no "ph_stretch".  tempo: None, a number, or one number per item, finite and > 0 (ValueError);
@@ -234,7 +273,7 @@ def retime_items(items, tempo, device, max_frames_per_batch=32768):
 @torch.no_grad()
 def synthesize(model, items, hop_size, max_frames_per_batch=32768, noise_scale=1.0, generator=None, equal_tokens=False,
                graphs=None, streams=2, seeds=None, takes=1, first_take=0, voicing="guide", pitch_shift_cents=None, return_f0=False,
-               tempo=None):
+               tempo=None, guide_track=None):
     """Run VISinger.forward(infer=True) over length-bucketed batches.  Returns a list of float32 waveforms trimmed to
     each item's own length (frames * hop_size), in the input order.
 
@@ -272,7 +311,17 @@ def synthesize(model, items, hop_size, max_frames_per_batch=32768, noise_scale=1
     Tempo control (timing.retime): tempo -- a number, or one per item in input order, > 0 -- and an item's "ph_stretch" -- one factor > 0 per token -- retime
     the item's mel2ph by ph_stretch[i] / tempo per token, and warp its "f0" with it, on the device in a pre-pass (retime_items); the call then runs on
     copies of the items that carry the retimed alignment, so buckets, `ragged`, graphs and trimming see the new lengths.  The caller's items are not
-    modified.  Without tempo and without an item that carries "ph_stretch" there is no pre-pass."""
+    modified.  Without tempo and without an item that carries "ph_stretch" there is no pre-pass.
+
+    Guide recordings (guide_items): an item may carry "guide_wav" -- a 1-D float array, a recording at the model's sample rate -- instead of "f0"; its curve is
+    tracked on the device in a pre-pass (pitch_track.extract_f0 with the keywords of guide_track, a dict that must contain sample_rate) and fitted to the item's
+    frames.  The pre-pass runs before the tempo pre-pass, so tempo and "ph_stretch" warp a tracked curve exactly as they warp a given one; the caller's items are
+    not modified.  ValueError: an item with "guide_wav" and no guide_track (or one without sample_rate), an item with both "f0" and "guide_wav", a recording that
+    is not 1-D or shorter than hop_size.  Without "guide_wav" in any item nothing changes."""
+    if any(it.get("guide_wav") is not None for it in items):
+        if guide_track is None or "sample_rate" not in guide_track:
+            raise ValueError("an item carries 'guide_wav': give guide_track, a dict of pitch_track.extract_f0 keywords with sample_rate")
+        items = guide_items(items, hop_size, next(model.parameters()).device, max_frames_per_batch, **guide_track)
     if tempo is not None or any(it.get("ph_stretch") is not None for it in items):
         items = retime_items(items, tempo, next(model.parameters()).device, max_frames_per_batch)
     if voicing not in ("guide", "model"):
