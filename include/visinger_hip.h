@@ -425,6 +425,45 @@ VS_API int vs_f0_yin(const float *wav, const int64_t *lengths, int64_t B, int64_
                      float threshold, float silence, float *f0_hz, float *periodicity, int64_t T, void *stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * f7  guide alignment (csrc/guide_align.hip): the score timed to a recording -- which frames of a guide curve (f6's output, on its OWN timeline)
+ *     belong to which token, as new frames-per-token that vs_retime_tokens(dur =) turns into an alignment.  Not in the reference (its inference replays the score's
+ *     timing; alignment is an offline host tool).  A monotonic Viterbi alignment; integer once the two inputs are quantised, so it is reproducible bit for bit.
+ *     Per item b:  f0_hz fp32 [B, Tg];  g_len DEVICE int64 [B] or NULL (= Tg), clamped to [0, Tg]: G;  note_midi fp32 [B, T_ph]: the score pitch of each token as
+ *     a MIDI number (fractions allowed), not finite or <= 0 = a rest (rests and padding);  dur int64 [B, T_ph]: score frames per token, read clamped to [0, 2^24);
+ *     offset_cents DEVICE fp32 [B] or NULL (0): the guide's transposition against the score.  Outputs, every element written: dur_new int64 [B, T_ph],
+ *     cost int32 [B], status int32 [B].
+ *       Quantisation (unit: 1/16 semitone).  Frame t is voiced when f0 is finite and > 0; then q_t = (int) rintf(x) + 1104, x = 192 log2f(f0 / 440) (the accurate
+ *       log2f, one fp32 division, one fp32 product) clamped to [-40000, 40000].  Pitched token: m_i = (int) rintf(min(16 note_midi, 2^20)).
+ *       off = (int) rintf(clamp(offset_cents * 0.16f, -2^20, 2^20)), 0 for a non-finite offset.
+ *       Active tokens: those with dur > 0, in order; S their count, d_s their durations, a_s the exclusive prefix sum of d, L = sum d.
+ *       S == 0 or G < S:  status = 1, dur_new = max(dur, 0) (as given, not clamped above), cost = -1.  Otherwise status = 0 and:
+ *       Local cost c(t, s) = pitch term + drift term.
+ *         pitch: voiced frame, pitched token: delta = abs(q_t - m_s - off); with octave_fold: delta %= 192, delta = min(delta, 192 - delta); min(delta, cap);
+ *                voiced, rest: w_voiced_rest;  unvoiced, pitched: w_unvoiced_note;  unvoiced, rest: 0.
+ *         drift: u_t = floor(t L / G) (int64);  gap = max(0, a_s - u_t, u_t - (a_s + d_s - 1));  min((gap drift) >> 8, drift_cap).
+ *       Recurrence, int32, INF = 2^30 - 1:  D(0, 0) = c(0, 0), D(0, s > 0) = INF;  for t >= 1: adv(t, s) = s > 0 && D(t-1, s-1) < D(t-1, s) (a tie stays),
+ *         D(t, s) = min(INF, c(t, s) + (adv ? D(t-1, s-1) : D(t-1, s)));  cost = D(G-1, S-1).
+ *       Backtrack: s = S-1; for t = G-1 .. 1: if adv(t, s): start[s] = t, s -= 1.  start[0] = 0, start[S] = G, n_s = start[s+1] - start[s] (>= 1).
+ *       Runs (pitch cannot separate a consonant from the vowel of its note): a run is a maximal stretch of consecutive active tokens that are all rests, or all
+ *         pitched with equal m.  In a run of k tokens with n = sum n_s, D_r = sum d_s and cumulative C_i (i = 1 .. k), int64, floor division:
+ *         E_0 = 0;  R_i = min((2 C_i n + D_r) / (2 D_r), n - (k - i));  E_i = max(E_{i-1} + 1, R_i);  token i of the run gets E_i - E_{i-1} (E_k = n, each >= 1).
+ *       Inactive tokens get 0: sum dur_new[b] = G.
+ *     Weights: cap, w_voiced_rest, w_unvoiced_note, drift, drift_cap in [0, 4096] (defaults 64, 48, 24, 32, 64), octave_fold 0 / 1, reserved = 0.
+ *     One workgroup per item, one launch: sequential over the frames, one column of D per lane, the neighbour by a lane shift and across waves through LDS (one
+ *     barrier a frame, none when S <= 64).  Backpointers are one bit per (t, s), a wave's ballot per 64 columns: in LDS when G ceil(S / 64) <=
+ *     VS_GUIDE_ALIGN_LDS_WORDS, else in `workspace`, laid out [B, Tg, ceil(T_ph / 64)] 64-bit words and written by plain stores.  The workspace (8-byte aligned,
+ *     workspace_bytes >= B Tg ceil(T_ph / 64) 8) is REQUIRED when Tg ceil(T_ph / 64) > VS_GUIDE_ALIGN_LDS_WORDS and not looked at otherwise.
+ *     An item's outputs depend on its own row's first G frames and T_ph tokens only.
+ *     VS_EINVAL before anything is launched: NULL f0_hz / note_midi / dur / dur_new / cost / status, aliased buffers, B < 1, T_ph outside [1, 1024], Tg outside
+ *     [1, 65536], a weight outside [0, 4096], octave_fold not 0 / 1, reserved != 0, a required workspace that is NULL, misaligned or too small.  No allocation,
+ *     no atomics, no host synchronisation; f0_hz, g_len, note_midi, dur, offset_cents are read on the device: a captured graph replays on another guide by
+ *     overwriting them.                                                                                                                                  */
+#define VS_GUIDE_ALIGN_LDS_WORDS 5120
+VS_API int vs_guide_align(const float *f0_hz, const int64_t *g_len, const float *note_midi, const int64_t *dur, const float *offset_cents, int cap,
+                          int w_voiced_rest, int w_unvoiced_note, int drift, int drift_cap, int octave_fold, int reserved, int64_t *dur_new, int32_t *cost,
+                          int32_t *status, void *workspace, size_t workspace_bytes, int64_t B, int64_t Tg, int64_t T_ph, void *stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * a13 grouped / strided Conv1d of the scale discriminator (modules/discriminator.py:55-60) and its gradients.
  *     x: [B, c_in, T], w: [c_out, c_in/groups, k], y / gy: [B, c_out, T_out], T_out = (T + 2*pad - k)/stride + 1.
  *     vs_gconv1d_bwd_weight writes one plane per batch item, gw_planes [B][c_out, c_in/groups, k]; gw = their sum.

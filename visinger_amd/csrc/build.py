@@ -20,7 +20,9 @@ NO_SCRATCH = {"conv_split.hip": "conv_split_kernel",
               "resblock_f16.hip": "resblock_",                # resblock_f16_kernel and resblock_bf16_kernel
               # (a spill inside the chunk body would sit between MFMAs that leave it no issue slot; ADVICE r4: the LDS-DMA ring of the attention
               #  kernel counts its vector-memory operations by hand as well)
-              "conv_ktap.hip": "conv_ktap_kernel", "conv_ktap_bf16.hip": "conv_ktap_kernel", "conv_ktap_small.hip": "conv_ktap_kernel", "conv_ktap_pair.hip": "conv_ktap_kernel", "attention_dma.hip": "relattn_dma_kernel"}
+              "conv_ktap.hip": "conv_ktap_kernel", "conv_ktap_bf16.hip": "conv_ktap_kernel", "conv_ktap_small.hip": "conv_ktap_kernel", "conv_ktap_pair.hip": "conv_ktap_kernel", "attention_dma.hip": "relattn_dma_kernel",
+              # (a dependent chain of G frame steps in a 1024-thread workgroup, 128 registers a lane: a spill would be paid once per frame)
+              "guide_align.hip": "guide_align_kernel"}
 
 
 def check_no_scratch(src, remarks):

@@ -5,6 +5,7 @@ int16).  Host-side plumbing only."""
 import numpy as np
 import torch
 
+from . import guide_align as guide_align_ops
 from . import pitch, pitch_track, sampling, timing
 
 
@@ -190,11 +191,12 @@ class GraphedStep:
         return self.out          # the graph's STATIC output buffer: the next replay overwrites it (clone to keep it)
 
 
-def guide_items(items, hop_size, device, max_frames_per_batch=32768, **track):
+def guide_items(items, hop_size, device, max_frames_per_batch=32768, fit=True, **track):
     """Copies of `items` in which a recording "guide_wav" -- a 1-D float array at the model's sample rate -- is replaced by "f0": its pitch curve, tracked on
     the device (pitch_track.extract_f0(**track), which needs sample_rate) in length buckets -- zero-padded, the lengths in a device tensor -- read back and fitted
     to the item's len(mel2ph): a longer curve is cut there, a shorter one padded with 0 (unvoiced: vs_f0_norm_interp bridges it like any gap).  Items without a
-    recording are passed on as they are.  ValueError: no sample_rate, an item with both "f0" and "guide_wav", a recording that is not 1-D or shorter than a hop."""
+    recording are passed on as they are.  fit=False: the curve keeps its own len(guide_wav) // hop_size frames, the recording's timeline (align_items
+    takes it from there).  ValueError: no sample_rate, an item with both "f0" and "guide_wav", a recording that is not 1-D or shorter than a hop."""
     if "sample_rate" not in track:
         raise ValueError("guide_track must contain sample_rate (the rate of the recordings, which is the model's)")
     if set(track) - {"sample_rate", "f0_min", "f0_max", "window", "threshold", "silence"}:
@@ -221,11 +223,77 @@ def guide_items(items, hop_size, device, max_frames_per_batch=32768, **track):
         lens = torch.tensor([len(wavs[i]) for i in idx], dtype=torch.int64).to(device)
         f0 = pitch_track.extract_f0(wav.to(device), hop_size, lengths=lens, **track).cpu().numpy()
         for b, i in enumerate(idx):
-            T, have = len(items[i]["mel2ph"]), min(len(wavs[i]) // hop_size, len(items[i]["mel2ph"]))
+            own = len(wavs[i]) // hop_size
+            T, have = (len(items[i]["mel2ph"]), min(own, len(items[i]["mel2ph"]))) if fit else (own, own)
             curve = np.zeros(T, np.float32)
             curve[:have] = f0[b, :have]
             del out[i]["guide_wav"]
             out[i]["f0"] = curve
+    return out
+
+
+def align_items(items, device, max_frames_per_batch=32768, **guide_align):
+    """Copies of `items` in which an item that carries a guide curve "f0" -- any length >= 1, on the guide's own timeline -- and token pitches is timed to
+    that curve (guide_align.align_guide): its "mel2ph" is replaced by timing.retime(dur=dur_new) -- exact, no stretch, no tempo -- so it has
+    len(f0) frames and the curve is a guide on it as it is; "f0" is kept.  Token pitches: the item's "note_midi", one MIDI number per token (<= 0 or not finite
+    = a rest), or its "pitch_tokens" mapped through guide_align["midi_of_token"] (a sequence indexed by token id).  Items without a curve or without token
+    pitches are passed on as they are.  The other keywords are align_guide's: offset_cents (one number for the call; an item's "guide_offset_cents" goes
+    before it), octave_fold and the weights.  Computed on the device in buckets of guide length and read back.
+    ValueError: an unknown keyword, a curve that is not 1-D or longer than 65536 frames, an item of more than 1024 tokens, "note_midi" of another length than
+    the tokens, a pitch token outside midi_of_token, and an item that cannot be aligned (status 1: no token with frames, or fewer guide frames than such
+    tokens) -- named by its index."""
+    table = guide_align.pop("midi_of_token", None)
+    offset = guide_align.pop("offset_cents", 0.0)
+    if set(guide_align) - set(guide_align_ops.DEFAULTS):
+        raise ValueError(f"guide_align takes midi_of_token, offset_cents, {', '.join(guide_align_ops.DEFAULTS)}, got {sorted(guide_align)}")
+    guide_align_ops.check_args(**guide_align)
+    if not (isinstance(offset, (int, float)) and abs(offset) < float("inf")):
+        raise ValueError(f"offset_cents must be a finite number, got {offset!r}")
+    table = None if table is None else np.asarray(table, dtype=np.float32)
+    if table is not None and table.ndim != 1:
+        raise ValueError(f"midi_of_token must be a 1-D sequence of MIDI numbers indexed by pitch token, got shape {table.shape}")
+    out = [dict(it) for it in items]
+    notes, curves = {}, {}
+    for i, it in enumerate(items):
+        if it.get("f0") is None or (it.get("note_midi") is None and table is None):
+            continue
+        n_tok = len(it["text_tokens"])
+        if it.get("note_midi") is not None:
+            nm = np.asarray(it["note_midi"], dtype=np.float32)
+            if nm.shape != (n_tok,):
+                raise ValueError(f"item {i}: note_midi has shape {nm.shape} for {n_tok} tokens (one MIDI number per token)")
+        else:
+            pt = np.asarray(it["pitch_tokens"]).astype(np.int64)
+            if pt.shape != (n_tok,) or (pt < 0).any() or (pt >= len(table)).any():
+                raise ValueError(f"item {i}: pitch_tokens must be {n_tok} ids in [0, {len(table)}) to go through midi_of_token")
+            nm = table[pt]
+        f0 = np.asarray(it["f0"], dtype=np.float32)
+        if f0.ndim != 1 or not 1 <= len(f0) <= guide_align_ops.TG_LIMIT or not 1 <= n_tok <= guide_align_ops.T_PH_LIMIT:
+            raise ValueError(f"item {i}: a guide curve of 1 .. {guide_align_ops.TG_LIMIT} frames (1-D) and 1 .. {guide_align_ops.T_PH_LIMIT} tokens can be aligned, "
+                             f"got {f0.shape} and {n_tok}")
+        notes[i], curves[i] = nm, f0
+    order = list(notes)
+    for idx in bucket_by_length([len(curves[i]) for i in order], max_frames_per_batch):
+        idx = [order[j] for j in idx]
+        B, Tg = len(idx), max(len(curves[i]) for i in idx)
+        T_ph, T = max(len(notes[i]) for i in idx), max(1, max(len(items[i]["mel2ph"]) for i in idx))
+        f0, nm = torch.zeros((B, Tg), dtype=torch.float32), torch.zeros((B, T_ph), dtype=torch.float32)
+        m2p = torch.zeros((B, T), dtype=torch.long)
+        for b, i in enumerate(idx):
+            f0[b, :len(curves[i])], nm[b, :len(notes[i])] = torch.from_numpy(curves[i]), torch.from_numpy(notes[i])
+            m2p[b, :len(items[i]["mel2ph"])] = torch.as_tensor(np.asarray(items[i]["mel2ph"]), dtype=torch.long)
+        cents = [float(items[i].get("guide_offset_cents", offset)) for i in idx]
+        dur_new, _, status = guide_align_ops.align_guide(f0.to(device), nm.to(device), mel2ph=m2p.to(device), guide_lengths=[len(curves[i]) for i in idx],
+                                                         offset_cents=cents, **guide_align)
+        status = status.cpu().tolist()
+        if any(status):
+            b = status.index(1)
+            raise ValueError(f"item {idx[b]} cannot be aligned: a guide of {len(curves[idx[b]])} frames for a score whose alignment gives "
+                             f"{len(set(np.asarray(items[idx[b]]['mel2ph']).tolist()) - {0})} tokens frames (at least one frame per such token is needed)")
+        new, lens, _ = timing.retime(dur=dur_new)
+        new, lens = new.cpu().numpy(), lens.cpu().tolist()
+        for b, i in enumerate(idx):
+            out[i]["mel2ph"] = new[b, :lens[b]].copy()
     return out
 
 
@@ -273,7 +341,7 @@ def retime_items(items, tempo, device, max_frames_per_batch=32768):
 @torch.no_grad()
 def synthesize(model, items, hop_size, max_frames_per_batch=32768, noise_scale=1.0, generator=None, equal_tokens=False,
                graphs=None, streams=2, seeds=None, takes=1, first_take=0, voicing="guide", pitch_shift_cents=None, return_f0=False,
-               tempo=None, guide_track=None):
+               tempo=None, guide_track=None, guide_align=None):
     """Run VISinger.forward(infer=True) over length-bucketed batches.  Returns a list of float32 waveforms trimmed to
     each item's own length (frames * hop_size), in the input order.
 
@@ -317,11 +385,22 @@ def synthesize(model, items, hop_size, max_frames_per_batch=32768, noise_scale=1
     tracked on the device in a pre-pass (pitch_track.extract_f0 with the keywords of guide_track, a dict that must contain sample_rate) and fitted to the item's
     frames.  The pre-pass runs before the tempo pre-pass, so tempo and "ph_stretch" warp a tracked curve exactly as they warp a given one; the caller's items are
     not modified.  ValueError: an item with "guide_wav" and no guide_track (or one without sample_rate), an item with both "f0" and "guide_wav", a recording that
-    is not 1-D or shorter than hop_size.  Without "guide_wav" in any item nothing changes."""
+    is not 1-D or shorter than hop_size.  Without "guide_wav" in any item nothing changes.
+
+    Guide alignment (align_items): guide_align -- a dict of align_items keywords, possibly empty -- times the score to the guide.  A recording's curve then
+    keeps its own len(guide_wav) // hop_size frames (guide_items(fit=False)), and every item with a curve ("f0" given, of any length, or tracked) and token
+    pitches ("note_midi", or "pitch_tokens" through guide_align["midi_of_token"]) gets the alignment the curve's timing implies: it is sung with the
+    recording's timing and the recording's pitch, len(f0) frames long.  The pre-pass runs between the guide and the tempo pre-pass, so tempo and "ph_stretch"
+    act on the aligned item; buckets, `ragged`, graphs and trimming see the new lengths; "dur_tokens" stay the caller's.  ValueError: see align_items.
+    With guide_align=None nothing changes."""
+    if guide_align is not None and not isinstance(guide_align, dict):
+        raise ValueError(f"guide_align must be a dict of align_items keywords (possibly empty) or None, got {guide_align!r:.60}")
     if any(it.get("guide_wav") is not None for it in items):
         if guide_track is None or "sample_rate" not in guide_track:
             raise ValueError("an item carries 'guide_wav': give guide_track, a dict of pitch_track.extract_f0 keywords with sample_rate")
-        items = guide_items(items, hop_size, next(model.parameters()).device, max_frames_per_batch, **guide_track)
+        items = guide_items(items, hop_size, next(model.parameters()).device, max_frames_per_batch, fit=guide_align is None, **guide_track)
+    if guide_align is not None:
+        items = align_items(items, next(model.parameters()).device, max_frames_per_batch, **guide_align)
     if tempo is not None or any(it.get("ph_stretch") is not None for it in items):
         items = retime_items(items, tempo, next(model.parameters()).device, max_frames_per_batch)
     if voicing not in ("guide", "model"):
