@@ -2,7 +2,8 @@
 pre-packed K / V tile images brought into an LDS ring by LDS-DMA.  Same algorithm and arithmetic as relattn_bf16_kernel<DT, 32, 1, true>
 except for the summation order of the score tile (even / odd k-steps in two accumulators): held to the same stated bf16 bounds against the
 exact-fp32 kernel (which the reference's golden vectors and the fp64 oracle pin), and to a much tighter bound against the kernel it
-replaces -- the two round the same bf16 operands, so they differ by fp32 summation order and by the bf16 probabilities that flip on it."""
+replaces -- the two round the same bf16 operands, so they differ by fp32 summation order and by the bf16 probabilities that flip on it.
+(Element by element against a bf16-operand reference, at 2e-5 * (1 + |ref|): tests/test_attention_bf16_oracle_gpu.py.)"""
 import pytest
 import torch
 

@@ -381,9 +381,11 @@ def weightnorm_fold(v, g):
     return w
 
 
-def rel_attention(qkv, n_heads, rel_k=None, rel_v=None, mask=None, window_size=None, out=None, math=L.MATH_F32, ksplit_auto=True):
+def rel_attention(qkv, n_heads, rel_k=None, rel_v=None, mask=None, window_size=None, out=None, math=L.MATH_F32, ksplit_auto=True, work=None):
     """a6: attention core on a fused [B, 3C, T] q|k|v buffer -> [B, C, T].  math = L.MATH_BF16: both GEMMs on the bf16 matrix
-    instruction (the arithmetic of the q / k / v convs around it, BASELINE config 5); otherwise exact fp32."""
+    instruction (the arithmetic of the q / k / v convs around it, BASELINE config 5); otherwise exact fp32.
+    work: the caller's buffer for the key split's partial rows, used instead of a fresh one -- like `out`, the caller sees it afterwards
+    (fp32, B * heads * ranges * (C / heads + 2 + window rows) * T elements or more; untouched by a launch that does not split its keys)."""
     lib = L.require_gpu()
     B, C3, T = qkv.shape
     C = C3 // 3
@@ -398,10 +400,15 @@ def rel_attention(qkv, n_heads, rel_k=None, rel_v=None, mask=None, window_size=N
         ksplit = max(1, min(8, 256 // nwg, T // 128))
         if L.switch("VS_ATTN_KSPLIT"):
             ksplit = max(1, min(16, L.switch("VS_ATTN_KSPLIT"), T // 64))
-    work = None
     if ksplit > 1:
         R = 0 if rel_k is None else rel_k.shape[1]
-        work = torch.empty((B * n_heads * ksplit * (C // n_heads + 2 + R) * T,), device=qkv.device, dtype=torch.float32)
+        need = B * n_heads * ksplit * (C // n_heads + 2 + R) * T
+        if work is None:
+            work = torch.empty((need,), device=qkv.device, dtype=torch.float32)
+        elif work.dtype != torch.float32 or not work.is_contiguous() or work.numel() < need or work.device != qkv.device:
+            raise ValueError(f"rel_attention: work must be a contiguous fp32 buffer of at least {need} elements on {qkv.device}")
+    else:
+        work = None
     # plain-bf16 arithmetic on long sequences: scratch for the K / V tile images the library then packs once per launch instead of once
     # per query block (vs_relattn_fwd_work); 0 bytes: not applicable
     kv_bytes = int(lib.vs_relattn_kv_work_bytes(B, n_heads, C // n_heads, T, int(math)))
