@@ -464,6 +464,49 @@ VS_API int vs_guide_align(const float *f0_hz, const int64_t *g_len, const float 
                           int32_t *status, void *workspace, size_t workspace_bytes, int64_t B, int64_t Tg, int64_t T_ph, void *stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * f8  guide pitch correction (csrc/guide_correct.hip): a tracked guide curve pulled onto the score it was sung to -- the slow part of its
+ *     deviation from the note (a flat note, drift) is taken out, the fast part (vibrato, scoops, jitter) is kept or scaled.  Not in the reference (its pitch
+ *     tools are offline host programs).  Integer once the inputs are quantised, so it is reproducible bit for bit.  The conventions are f7's.
+ *     Per item b:  f0_hz fp32 [B, T], on the item's own frames;  mel2ph int64 [B, T]: 1-based token ids, 0 = padding;  note_midi fp32 [B, T_ph]: not finite or
+ *     <= 0 = a rest;  lengths DEVICE int64 [B] or NULL (= T), clamped to [0, T]: n;  offset_cents DEVICE fp32 [B] or NULL (0): the guide's transposition against
+ *     the score.  Host parameters: window W in [0, 1024] frames, strength_q a in [0, 256], vibrato_q in [0, 512] with b = 256 - vibrato_q, wild in [0, 2^18]
+ *     units, octave_fold 0 / 1, reserved = 0.
+ *       Quantisation (unit: 1/16 cent -- 19200 an octave, 1600 a semitone).  Frame t is voiced when f0 is finite and > 0; then
+ *       q_t = (int) rintf(clamp(19200 log2f(f0 / 440), -2^22, 2^22)) (the accurate log2f, one fp32 division, one fp32 product).  Frame t has the token mel2ph[t]
+ *       when that lies in [1, T_ph], else none.  Pitched token: m = (int) rintf(clamp(1600 (note_midi - 69), -2^22, 2^22)) (one fp32 difference, one fp32
+ *       product).  off = (int) rintf(clamp(16 offset_cents, -2^22, 2^22)), 0 for a non-finite offset.
+ *       Deviation.  d_t = q_t - m_t - off;  with octave_fold: d_t -= 19200 floor((d_t + 9600) / 19200).  Frame t < n is CORRECTABLE when it is voiced, its token
+ *       is pitched and |d_t| <= wild.
+ *       Segments.  A segment is a maximal stretch of consecutive frames t < n whose tokens are pitched with equal m (f7's run: consonant and vowel of a note,
+ *       two equal notes in a row).  Unvoiced or wild frames inside a segment do not split it; they do not count.
+ *       Slow part.  For a correctable t: S_t = the sum of d_u and N_t the count over the correctable u of t's segment with |u - t| <= W (N_t >= 1);
+ *       s_t = floor((2 S_t + N_t) / (2 N_t));  v_t = d_t - s_t.
+ *       Correction.  k_t = floor((a s_t + b v_t + 128) / 256);  f0_out = f0 exp2f((float)(-k_t) / 19200.0f) (one fp32 division, the accurate exp2f, one fp32
+ *       product).  Where k_t == 0, and on every frame that is not correctable -- t >= n, NaNs and negative values included -- f0_out is the bits of f0_hz and
+ *       k_out is 0.  (a = 256, b = 0: the windowed mean of every note moves onto the score and what is faster stays;  a = 0, b = 0: the identity, bit for bit;
+ *       b = 256: flattened;  b = -256: the fast part doubled.)
+ *       With wild <= 2^18 and W <= 1024 every intermediate fits int32: |d| <= 2^18, |S| <= 2049 2^18, |2 S + N| < 2^31, |a s| <= 2^26, |b v| <= 2^27.
+ *     vs_guide_correct: f0_out fp32 [B, T], k_out int32 [B, T] or NULL; every element of both is written.  One launch: grid (tiles of VS_GUIDE_CORRECT_TILE
+ *     frames, B); a workgroup stages its tile plus a halo of W frames on both sides (d, the flags, m -- note_midi gathered through mel2ph) into LDS, forms the
+ *     prefix sums of d and of the flags, the prefix max of the segment starts and the suffix min of the segment ends in one workgroup scan, and takes S_t, N_t as
+ *     differences at the clipped window's ends (a boundary farther than W away never matters: the halo is enough).  16-byte loads and stores when T % 4 == 0 and
+ *     f0_hz, mel2ph, f0_out, k_out are 16-byte aligned.
+ *     vs_guide_deviation: per item n_corr = the number of correctable frames and dev_med = the LOWER median of d_t over them -- the element at index
+ *     (n_corr - 1) / 2 of the sorted values -- or 0 when there are none (int32 [B] each).  With offset_cents = NULL and a large wild, dev_med / 16 is the guide's
+ *     transposition against the score in cents.  One workgroup per item: a bisection on the value over [-wild, wild], each step one count over the item's frames.
+ *     A row's outputs depend on its own first n frames and its T_ph tokens only.
+ *     VS_EINVAL before anything is launched, the outputs untouched: a NULL f0_hz / mel2ph / note_midi / f0_out (dev_med / n_corr), an output that overlaps an
+ *     input or the other output, B < 1, T outside [1, 65536], T_ph outside [1, 1024], a parameter out of its range, reserved != 0.  No allocation, no atomics,
+ *     no host synchronisation; f0_hz, lengths, mel2ph, note_midi, offset_cents are read on the device: a captured graph replays on another guide by overwriting
+ *     them.                                                                                                                                               */
+#define VS_GUIDE_CORRECT_TILE 1024
+VS_API int vs_guide_correct(const float *f0_hz, const int64_t *lengths, const int64_t *mel2ph, const float *note_midi, const float *offset_cents, int window,
+                            int strength_q, int vibrato_q, int wild, int octave_fold, int reserved, float *f0_out, int32_t *k_out, int64_t B, int64_t T,
+                            int64_t T_ph, void *stream);
+VS_API int vs_guide_deviation(const float *f0_hz, const int64_t *lengths, const int64_t *mel2ph, const float *note_midi, const float *offset_cents, int wild,
+                              int octave_fold, int32_t *dev_med, int32_t *n_corr, int64_t B, int64_t T, int64_t T_ph, void *stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * a13 grouped / strided Conv1d of the scale discriminator (modules/discriminator.py:55-60) and its gradients.
  *     x: [B, c_in, T], w: [c_out, c_in/groups, k], y / gy: [B, c_out, T_out], T_out = (T + 2*pad - k)/stride + 1.
  *     vs_gconv1d_bwd_weight writes one plane per batch item, gw_planes [B][c_out, c_in/groups, k]; gw = their sum.

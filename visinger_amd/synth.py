@@ -6,6 +6,7 @@ import numpy as np
 import torch
 
 from . import guide_align as guide_align_ops
+from . import guide_correct as guide_correct_ops
 from . import pitch, pitch_track, sampling, timing
 
 
@@ -297,6 +298,73 @@ def align_items(items, device, max_frames_per_batch=32768, **guide_align):
     return out
 
 
+def correct_items(items, device, max_frames_per_batch=32768, **guide_correct):
+    """Copies of `items` in which the guide curve "f0" of an item that carries one -- one value per frame of its mel2ph -- and token pitches is pulled onto the
+    score (guide_correct.correct_guide): the slow part of its deviation from each note is taken out, vibrato and scoops stay.  Token pitches:
+    the item's "note_midi", one MIDI number per token (<= 0 or not finite = a rest), or its "pitch_tokens" mapped through guide_correct["midi_of_token"] (a
+    sequence indexed by token id), as in align_items.  Items without a curve or without token pitches are passed on as they are.  The other keywords are
+    correct_guide's: window, strength, vibrato, wild_cents, octave_fold, and offset_cents -- one number for the call, or "auto" (each item in the key it was
+    sung in); an item's "guide_offset_cents" goes before it.  Computed on the device in buckets of length and read back.
+    ValueError: an unknown keyword, a value out of range, a curve that is not 1-D with len(mel2ph) values, an item of more than 65536 frames or 1024 tokens,
+    "note_midi" of another length than the tokens, a pitch token outside midi_of_token -- named by the item's index."""
+    table = guide_correct.pop("midi_of_token", None)
+    offset = guide_correct.pop("offset_cents", 0.0)
+    if set(guide_correct) - set(guide_correct_ops.DEFAULTS):
+        raise ValueError(f"guide_correct takes midi_of_token, offset_cents, {', '.join(guide_correct_ops.DEFAULTS)}, got {sorted(guide_correct)}")
+    guide_correct_ops.check_args(**guide_correct)
+    auto = isinstance(offset, str) and offset == "auto"
+    if not auto and not (isinstance(offset, (int, float)) and abs(offset) < float("inf")):
+        raise ValueError(f"offset_cents must be a finite number or 'auto', got {offset!r}")
+    table = None if table is None else np.asarray(table, dtype=np.float32)
+    if table is not None and table.ndim != 1:
+        raise ValueError(f"midi_of_token must be a 1-D sequence of MIDI numbers indexed by pitch token, got shape {table.shape}")
+    out = [dict(it) for it in items]
+    notes, curves = {}, {}
+    for i, it in enumerate(items):
+        if it.get("f0") is None or (it.get("note_midi") is None and table is None):
+            continue
+        n_tok, n_frames = len(it["text_tokens"]), len(it["mel2ph"])
+        if it.get("note_midi") is not None:
+            nm = np.asarray(it["note_midi"], dtype=np.float32)
+            if nm.shape != (n_tok,):
+                raise ValueError(f"item {i}: note_midi has shape {nm.shape} for {n_tok} tokens (one MIDI number per token)")
+        else:
+            pt = np.asarray(it["pitch_tokens"]).astype(np.int64)
+            if pt.shape != (n_tok,) or (pt < 0).any() or (pt >= len(table)).any():
+                raise ValueError(f"item {i}: pitch_tokens must be {n_tok} ids in [0, {len(table)}) to go through midi_of_token")
+            nm = table[pt]
+        f0 = np.asarray(it["f0"], dtype=np.float32)
+        if f0.shape != (n_frames,):
+            raise ValueError(f"item {i}: the guide curve has {f0.shape} values for {n_frames} frames (one value in Hz per frame)")
+        if not 1 <= n_frames <= guide_correct_ops.T_LIMIT or not 1 <= n_tok <= guide_correct_ops.T_PH_LIMIT:
+            raise ValueError(f"item {i}: a guide curve of 1 .. {guide_correct_ops.T_LIMIT} frames and 1 .. {guide_correct_ops.T_PH_LIMIT} tokens can be "
+                             f"corrected, got {n_frames} and {n_tok}")
+        own = it.get("guide_offset_cents")
+        if own is not None and not (isinstance(own, (int, float)) and abs(own) < float("inf")):
+            raise ValueError(f"item {i}: guide_offset_cents must be a finite number, got {own!r}")
+        notes[i], curves[i] = nm, f0
+    order = list(notes)
+    for idx in bucket_by_length([len(curves[i]) for i in order], max_frames_per_batch):
+        idx = [order[j] for j in idx]
+        B, T, T_ph = len(idx), max(len(curves[i]) for i in idx), max(len(notes[i]) for i in idx)
+        f0, nm, m2p = torch.zeros((B, T), dtype=torch.float32), torch.zeros((B, T_ph), dtype=torch.float32), torch.zeros((B, T), dtype=torch.long)
+        for b, i in enumerate(idx):
+            f0[b, :len(curves[i])], nm[b, :len(notes[i])] = torch.from_numpy(curves[i]), torch.from_numpy(notes[i])
+            m2p[b, :len(curves[i])] = torch.as_tensor(np.asarray(items[i]["mel2ph"]), dtype=torch.long)
+        f0, nm, m2p = f0.to(device), nm.to(device), m2p.to(device)
+        lens = [len(curves[i]) for i in idx]
+        own = [items[i].get("guide_offset_cents") for i in idx]
+        cents = torch.tensor([float(0.0 if auto else offset) if v is None else float(v) for v in own], dtype=torch.float32).to(device)
+        if auto and any(v is None for v in own):                         # the key of every item that does not bring its own, never read back
+            med, _ = guide_correct_ops.guide_deviation(f0, m2p, nm, lengths=lens, wild_cents=guide_correct.get("wild_cents", 300.0),
+                                                       octave_fold=guide_correct.get("octave_fold", False))
+            cents = torch.where(torch.tensor([v is None for v in own]).to(device), med.float() / 16, cents)
+        new = guide_correct_ops.correct_guide(f0, m2p, nm, lengths=lens, offset_cents=cents, **guide_correct).cpu().numpy()
+        for b, i in enumerate(idx):
+            out[i]["f0"] = new[b, :len(curves[i])].copy()
+    return out
+
+
 def retime_items(items, tempo, device, max_frames_per_batch=32768):
     """Copies of `items` with "mel2ph" (and "f0", when present) retimed by the item's "ph_stretch" / its tempo (timing.retime), computed on the device in
     collated groups and read back; the copies carry no "ph_stretch".  tempo: None, a number, or one number per item, finite and > 0 (ValueError);
@@ -341,7 +409,7 @@ def retime_items(items, tempo, device, max_frames_per_batch=32768):
 @torch.no_grad()
 def synthesize(model, items, hop_size, max_frames_per_batch=32768, noise_scale=1.0, generator=None, equal_tokens=False,
                graphs=None, streams=2, seeds=None, takes=1, first_take=0, voicing="guide", pitch_shift_cents=None, return_f0=False,
-               tempo=None, guide_track=None, guide_align=None):
+               tempo=None, guide_track=None, guide_align=None, guide_correct=None):
     """Run VISinger.forward(infer=True) over length-bucketed batches.  Returns a list of float32 waveforms trimmed to
     each item's own length (frames * hop_size), in the input order.
 
@@ -392,7 +460,14 @@ def synthesize(model, items, hop_size, max_frames_per_batch=32768, noise_scale=1
     pitches ("note_midi", or "pitch_tokens" through guide_align["midi_of_token"]) gets the alignment the curve's timing implies: it is sung with the
     recording's timing and the recording's pitch, len(f0) frames long.  The pre-pass runs between the guide and the tempo pre-pass, so tempo and "ph_stretch"
     act on the aligned item; buckets, `ragged`, graphs and trimming see the new lengths; "dur_tokens" stay the caller's.  ValueError: see align_items.
-    With guide_align=None nothing changes."""
+    With guide_align=None nothing changes.
+
+    Guide correction (correct_items): guide_correct -- a dict of correct_items keywords, possibly empty -- pulls every guide curve ("f0" given, or tracked)
+    of an item with token pitches onto the score: flat notes and drift are taken out, vibrato and scoops stay.  The pre-pass runs after the
+    alignment pre-pass -- the curve must have one value per frame of the item's mel2ph, which an aligned item has -- and before the tempo pre-pass, so tempo
+    and "ph_stretch" warp the corrected curve.  The caller's items are not modified.  ValueError: see correct_items.  With guide_correct=None nothing changes."""
+    if guide_correct is not None and not isinstance(guide_correct, dict):
+        raise ValueError(f"guide_correct must be a dict of correct_items keywords (possibly empty) or None, got {guide_correct!r:.60}")
     if guide_align is not None and not isinstance(guide_align, dict):
         raise ValueError(f"guide_align must be a dict of align_items keywords (possibly empty) or None, got {guide_align!r:.60}")
     if any(it.get("guide_wav") is not None for it in items):
@@ -401,6 +476,8 @@ def synthesize(model, items, hop_size, max_frames_per_batch=32768, noise_scale=1
         items = guide_items(items, hop_size, next(model.parameters()).device, max_frames_per_batch, fit=guide_align is None, **guide_track)
     if guide_align is not None:
         items = align_items(items, next(model.parameters()).device, max_frames_per_batch, **guide_align)
+    if guide_correct is not None:
+        items = correct_items(items, next(model.parameters()).device, max_frames_per_batch, **guide_correct)
     if tempo is not None or any(it.get("ph_stretch") is not None for it in items):
         items = retime_items(items, tempo, next(model.parameters()).device, max_frames_per_batch)
     if voicing not in ("guide", "model"):
