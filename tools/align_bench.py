@@ -17,20 +17,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 from visinger_amd import guide_align  # noqa: E402
-
-
-def timed(fn, warmup, iters):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(iters)]
-    for a, b in evs:
-        a.record()
-        fn()
-        b.record()
-    torch.cuda.synchronize()
-    us = sorted(a.elapsed_time(b) * 1e3 for a, b in evs)
-    return us[len(us) // 2], us[0]
+from _bench import emit, timed  # noqa: E402
 
 
 def score_and_guide(rng, G, T_ph):
@@ -93,9 +80,7 @@ def main():
                             ns_per_frame_step=round(1e3 * med / G, 1), host_numpy_one_item_ms=round(host_ms, 1), equal_to_restatement=same))
     line = {"tool": "align_bench", "warmup": args.warmup, "iters": args.iters, "results": results,
             "tracker_launch_us_32x1024": None if tracker is None else tracker.get("launch_us_median")}
-    print(json.dumps(line))
-    with open(args.out, "w") as f:
-        f.write(json.dumps(line) + "\n")
+    emit(line, args.out)
 
 
 if __name__ == "__main__":

@@ -5,7 +5,6 @@ correct_ref, deviation_ref) on ONE item, wall clock.
 HIP events around every launch, 10 warm-up + 50 timed; prints the median and the minimum per shape B x T x T_ph and window, and the effective bytes a second:
 what the launch must move once (f0 in and out 4 + 4 bytes a frame, mel2ph 8, k 4; the deviation: f0 4 + mel2ph 8) over the median.  Writes one JSON file."""
 import argparse
-import json
 import os
 import sys
 import time
@@ -17,20 +16,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 from visinger_amd import guide_correct  # noqa: E402
-
-
-def timed(fn, warmup, iters):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(iters)]
-    for a, b in evs:
-        a.record()
-        fn()
-        b.record()
-    torch.cuda.synchronize()
-    us = sorted(a.elapsed_time(b) * 1e3 for a, b in evs)
-    return us[len(us) // 2], us[0]
+from _bench import emit, timed  # noqa: E402
 
 
 def sung(rng, T, T_ph):
@@ -93,9 +79,7 @@ def main():
                                 launch_us_min=round(best, 1), effective_gb_per_s=round(gbs, 1), host_numpy_one_item_ms=round(host_ms, 2),
                                 equal_to_restatement=same))
     line = {"tool": "correct_bench", "warmup": args.warmup, "iters": args.iters, "results": results}
-    print(json.dumps(line))
-    with open(args.out, "w") as f:
-        f.write(json.dumps(line) + "\n")
+    emit(line, args.out)
 
 
 if __name__ == "__main__":

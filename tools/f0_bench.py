@@ -4,7 +4,6 @@ fp64 numpy restatement of the same rule (tests/test_f0_extract_cpu.py: yin_ref) 
 HIP events around every launch, 10 warm-up + 50 timed; prints the medians and one JSON line with the time per launch, frames/s and the fraction of the fp32
 VALU peak for 3 * W * (tau_max + 1) flop per frame (a subtract and a multiply-add per term).  Default: B = 32, T = 1024, hop 256, 24 kHz, 65 - 1000 Hz."""
 import argparse
-import json
 import os
 import sys
 import time
@@ -16,24 +15,11 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 from visinger_amd import pitch_track  # noqa: E402
+from _bench import emit, timed  # noqa: E402
 
 # MI355X fp32 vector peak (spec): 256 CUs x 4 SIMDs x 16 lanes x 2 (packed) x 2 flop (fma) at 2.4 GHz = 157.3 TFLOP/s.  A subtract and a multiply-add per term
 # are 3 flop in two instruction slots of 4, so 3/4 of it is this sum's own ceiling when every instruction is packed.
 VALU_PEAK_FLOPS = 256 * 4 * 16 * 2 * 2 * 2.4e9
-
-
-def timed(fn, warmup, iters):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(iters)]
-    for a, b in evs:
-        a.record()
-        fn()
-        b.record()
-    torch.cuda.synchronize()
-    us = sorted(a.elapsed_time(b) * 1e3 for a, b in evs)
-    return us[len(us) // 2], us[0]
 
 
 def main():
@@ -77,8 +63,8 @@ def main():
               f"{host_us / 1e3:.0f} ms; voiced {voiced:.2f}, voicing agrees with it on {same:.3f} of {k} frames", flush=True)
         results.append(dict(B=B, T=T, launch_us_median=round(med, 1), launch_us_min=round(best, 1), frames_per_s=round(B * T / (med * 1e-6)),
                             valu_peak_fraction=round(frac, 4), host_numpy_one_row_ms=round(host_us / 1e3, 1)))
-    print(json.dumps({"tool": "f0_bench", "hop": args.hop, "sr": args.sr, "f0_min": args.f0_min, "f0_max": args.f0_max, "window": W, "tau_max": tau_max,
-                      "flop_per_frame": flop_per_frame, "warmup": args.warmup, "iters": args.iters, "results": results}))
+    emit({"tool": "f0_bench", "hop": args.hop, "sr": args.sr, "f0_min": args.f0_min, "f0_max": args.f0_max, "window": W, "tau_max": tau_max,
+          "flop_per_frame": flop_per_frame, "warmup": args.warmup, "iters": args.iters, "results": results})
 
 
 if __name__ == "__main__":

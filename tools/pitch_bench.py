@@ -6,7 +6,6 @@
   restated here with numpy, wall-clock time including the two transfers, since that chain synchronises with the host by construction.
 HIP events around every iteration for the device-only paths, 20 warm-up + 100 timed; prints the medians and one JSON line.  Default: B = 32, T = 1024."""
 import argparse
-import json
 import os
 import sys
 import time
@@ -16,20 +15,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from visinger_amd import pitch  # noqa: E402
-
-
-def timed(fn, warmup, iters):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(iters)]
-    for a, b in evs:
-        a.record()
-        fn()
-        b.record()
-    torch.cuda.synchronize()
-    us = sorted(a.elapsed_time(b) * 1e3 for a, b in evs)
-    return us[len(us) // 2], us[0]
+from _bench import emit, timed  # noqa: E402
 
 
 def host_norm_interp(f0_dev, lengths):
@@ -99,7 +85,7 @@ def main():
               f"{i_med:.1f} us (min {i_min:.1f})", flush=True)
         results.append(dict(B=B, T=T, chain_us_median=round(c_med, 2), condition_us_median=round(k_med, 2), condition_full_us_median=round(f_med, 2),
                             host_interp_us_median=round(h_med, 1), interp_us_median=round(i_med, 2), interp_us_min=round(i_min, 2)))
-    print(json.dumps({"tool": "pitch_bench", "warmup": args.warmup, "iters": args.iters, "results": results}))
+    emit({"tool": "pitch_bench", "warmup": args.warmup, "iters": args.iters, "results": results})
 
 
 if __name__ == "__main__":

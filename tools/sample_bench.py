@@ -4,7 +4,6 @@
 [B, 2H, T] projection output and a [B, 1, T] frame mask.  HIP events around every iteration, 20 warm-up + 100 timed; prints the median and
 the minimum per shape and one JSON line.  Default shapes: the headline batch (B = 32, H = 192, T = 1024) and a single utterance (B = 1)."""
 import argparse
-import json
 import os
 import sys
 
@@ -12,20 +11,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from visinger_amd import sampling  # noqa: E402
-
-
-def timed(fn, warmup, iters):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(iters)]
-    for a, b in evs:
-        a.record()
-        fn()
-        b.record()
-    torch.cuda.synchronize()
-    us = sorted(a.elapsed_time(b) * 1e3 for a, b in evs)
-    return us[len(us) // 2], us[0]
+from _bench import emit, timed  # noqa: E402
 
 
 def main():
@@ -59,7 +45,7 @@ def main():
               f"{mb:.1f} MB -> {mb / k_med:.2f} TB/s at the median", flush=True)      # (MB / us = TB/s)
         results.append(dict(B=B, H=H, T=T, chain_us_median=round(c_med, 2), chain_us_min=round(c_min, 2), kernel_us_median=round(k_med, 2),
                             kernel_us_min=round(k_min, 2), kernel_tb_s=round(mb / k_med, 3)))
-    print(json.dumps({"tool": "sample_bench", "warmup": args.warmup, "iters": args.iters, "results": results}))
+    emit({"tool": "sample_bench", "warmup": args.warmup, "iters": args.iters, "results": results})
 
 
 if __name__ == "__main__":

@@ -5,7 +5,6 @@ host chain they replace, on the same inputs: per item the durations from mel2ph,
 -- wall clock, since that chain synchronises with the host by construction.
 HIP events around every iteration for the device path, 20 warm-up + 100 timed; prints the medians and one JSON line.  Default: B = 32, T = 1024, 128 tokens."""
 import argparse
-import json
 import os
 import sys
 import time
@@ -15,20 +14,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from visinger_amd import timing  # noqa: E402
-
-
-def timed(fn, warmup, iters):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(iters)]
-    for a, b in evs:
-        a.record()
-        fn()
-        b.record()
-    torch.cuda.synchronize()
-    us = sorted(a.elapsed_time(b) * 1e3 for a, b in evs)
-    return us[len(us) // 2], us[0]
+from _bench import emit, timed  # noqa: E402
 
 
 def host_retime(m2p_dev, curve_dev, stretch, tempo, T_ph, cap):
@@ -103,7 +89,7 @@ def main():
               flush=True)
         results.append(dict(B=B, T=T, T_ph=T_ph, capacity=cap, host_us_median=round(h_med, 1), retime_us_median=round(d_med, 2), retime_us_min=round(d_min, 2),
                             alignment_only_us_median=round(a_med, 2)))
-    print(json.dumps({"tool": "timing_bench", "warmup": args.warmup, "iters": args.iters, "results": results}))
+    emit({"tool": "timing_bench", "warmup": args.warmup, "iters": args.iters, "results": results})
 
 
 if __name__ == "__main__":

@@ -6,11 +6,9 @@ guide was sung in.  The reference has no counterpart (its pitch tools are offlin
 
 Everything that changes between two calls -- the curve, its length, the alignment, the note pitches, the offset -- is read from device tensors, so a captured
 graph replays on another guide by overwriting those buffers.  GPU tensors only; there is no CPU path and no backward."""
-import ctypes
-import numbers
-
 import torch
 
+from . import _args as A
 from . import _lib as L
 
 TILE = 1024                  # VS_GUIDE_CORRECT_TILE: frames a workgroup of vs_guide_correct writes
@@ -24,62 +22,35 @@ DEFAULTS = dict(window=1024, strength=1.0, vibrato=1.0, wild_cents=300.0, octave
 def check_args(window=1024, strength=1.0, vibrato=1.0, wild_cents=300.0, octave_fold=False):
     """ValueError for host values vs_guide_correct would refuse; returns the six ints of the C call: window, strength_q = round(256 strength),
     vibrato_q = round(256 vibrato), wild = round(16 wild_cents), octave_fold and the reserved 0"""
-    if not (isinstance(window, numbers.Integral) and not isinstance(window, bool) and 0 <= window <= WINDOW_LIMIT):
+    if not A.is_int(window, 0, WINDOW_LIMIT):
         raise ValueError(f"window must be an integer in [0, {WINDOW_LIMIT}] frames, got {window!r}")
     for name, v, top in (("strength", strength, 1.0), ("vibrato", vibrato, 2.0), ("wild_cents", wild_cents, WILD_LIMIT / 16.0)):
-        if not (isinstance(v, numbers.Real) and not isinstance(v, bool) and 0 <= v <= top):
+        if not A.is_real(v, 0, top):
             raise ValueError(f"{name} must be a number in [0, {top:g}], got {v!r}")
-    if not isinstance(octave_fold, (bool, numbers.Integral)) or octave_fold not in (0, 1):
+    if not (isinstance(octave_fold, bool) or A.is_int(octave_fold, 0, 1)):
         raise ValueError(f"octave_fold must be False or True, got {octave_fold!r}")
     return int(window), int(round(256 * float(strength))), int(round(256 * float(vibrato))), int(round(16 * float(wild_cents))), int(octave_fold), 0
 
 
-def _vp(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
-
-
 def _inputs(who, f0_hz, mel2ph, note_midi, lengths, offset_cents):
     """the checked, contiguous device tensors of a call (lengths and offset_cents possibly None) and B, T, T_ph"""
-    if not (torch.is_tensor(f0_hz) and f0_hz.is_cuda and f0_hz.dtype == torch.float32 and f0_hz.dim() == 2):
-        raise L.VisingerHipError(f"{who}: f0_hz must be an fp32 tensor [B, T] on the GPU (there is no CPU path), got {f0_hz!r:.80}")
+    f0_hz = A.gpu_tensor(who, "f0_hz", f0_hz, torch.float32, (None, None))
     B, T = f0_hz.shape
-    if not (torch.is_tensor(mel2ph) and mel2ph.is_cuda and mel2ph.dtype == torch.int64 and tuple(mel2ph.shape) == (B, T)):
-        raise L.VisingerHipError(f"{who}: mel2ph must be an int64 tensor [{B}, {T}] on the GPU, got {mel2ph!r:.80}")
-    if not (torch.is_tensor(note_midi) and note_midi.is_cuda and note_midi.dtype == torch.float32 and note_midi.dim() == 2 and note_midi.shape[0] == B):
-        raise L.VisingerHipError(f"{who}: note_midi must be an fp32 tensor [{B}, T_ph] on the GPU, got {note_midi!r:.80}")
+    mel2ph = A.gpu_tensor(who, "mel2ph", mel2ph, torch.int64, (B, T))
+    note_midi = A.gpu_tensor(who, "note_midi", note_midi, torch.float32, (B, None))
     T_ph = note_midi.shape[1]
     if B < 1 or not 1 <= T_ph <= T_PH_LIMIT or not 1 <= T <= T_LIMIT:
         raise L.VisingerHipError(f"{who}: B >= 1, 1 <= T_ph <= {T_PH_LIMIT} and 1 <= T <= {T_LIMIT} are required, got B = {B}, T_ph = {T_ph}, T = {T}")
-    dev = f0_hz.device
-    if torch.is_tensor(lengths) and lengths.is_cuda:
-        if not (lengths.dtype == torch.int64 and tuple(lengths.shape) == (B,)):
-            raise L.VisingerHipError(f"{who}: lengths as a GPU tensor must be int64 [{B}], got {lengths.dtype} {tuple(lengths.shape)}")
-        lengths = lengths.contiguous()
-    elif lengths is not None:
-        vals = [int(v) for v in (lengths.tolist() if torch.is_tensor(lengths) else lengths)]
-        if len(vals) != B or not all(0 <= v <= T for v in vals):
-            raise ValueError(f"lengths must be {B} integers in [0, {T}], got {vals if len(vals) <= 8 else vals[:8] + ['...']}")
-        lengths = torch.tensor(vals, dtype=torch.int64).to(dev)
-    if torch.is_tensor(offset_cents) and offset_cents.is_cuda:
-        if not (offset_cents.dtype == torch.float32 and tuple(offset_cents.shape) == (B,)):
-            raise L.VisingerHipError(f"{who}: offset_cents as a GPU tensor must be fp32 [{B}], got {offset_cents.dtype} {tuple(offset_cents.shape)}")
-        offset_cents = offset_cents.contiguous()
-    elif offset_cents is not None:
-        if torch.is_tensor(offset_cents):
-            offset_cents = offset_cents.tolist()
-        if isinstance(offset_cents, str):
-            raise ValueError(f"offset_cents must be a finite number, {B} of them, a GPU tensor or 'auto', got {offset_cents!r}")
-        vals = [float(offset_cents)] * B if isinstance(offset_cents, numbers.Real) else [float(v) for v in offset_cents]
-        if len(vals) != B or not all(abs(v) < float("inf") for v in vals):
-            raise ValueError(f"offset_cents must be a finite number, or {B} of them, got {vals if len(vals) <= 8 else vals[:8] + ['...']}")
-        offset_cents = torch.tensor(vals, dtype=torch.float32).to(dev)
-    return f0_hz.contiguous(), mel2ph.contiguous(), note_midi.contiguous(), lengths, offset_cents, B, T, T_ph
+    lengths = A.lengths_i64(who, "lengths", lengths, B, T, f0_hz.device)
+    if offset_cents is not None:
+        offset_cents = A.per_item_f32(f"{who}: offset_cents", offset_cents, B, f0_hz.device)
+    return f0_hz, mel2ph, note_midi, lengths, offset_cents, B, T, T_ph
 
 
 def _deviation(lib, f0_hz, mel2ph, note_midi, lengths, offset_cents, wild, octave_fold, B, T, T_ph):
     dev_med = torch.empty((B,), device=f0_hz.device, dtype=torch.int32)
     n_corr = torch.empty((B,), device=f0_hz.device, dtype=torch.int32)
-    L.check(lib.vs_guide_deviation(L.ptr(f0_hz), _vp(lengths), _vp(mel2ph), L.ptr(note_midi), L.ptr(offset_cents), wild, octave_fold, _vp(dev_med), _vp(n_corr),
+    L.check(lib.vs_guide_deviation(L.ptr(f0_hz), A.vp(lengths), A.vp(mel2ph), L.ptr(note_midi), L.ptr(offset_cents), wild, octave_fold, A.vp(dev_med), A.vp(n_corr),
                                    B, T, T_ph, L.stream_ptr()))
     return dev_med, n_corr
 
@@ -114,6 +85,6 @@ def correct_guide(f0_hz, mel2ph, note_midi, lengths=None, offset_cents=None, ret
         offset_cents = _deviation(lib, f0_hz, mel2ph, note_midi, lengths, None, wild, fold, B, T, T_ph)[0].float() / 16
     f0_out = torch.empty_like(f0_hz)
     k = torch.empty((B, T), device=f0_hz.device, dtype=torch.int32) if return_units else None
-    L.check(lib.vs_guide_correct(L.ptr(f0_hz), _vp(lengths), _vp(mel2ph), L.ptr(note_midi), L.ptr(offset_cents), window, strength_q, vibrato_q, wild, fold,
-                                 reserved, L.ptr(f0_out), _vp(k), B, T, T_ph, L.stream_ptr()))
+    L.check(lib.vs_guide_correct(L.ptr(f0_hz), A.vp(lengths), A.vp(mel2ph), L.ptr(note_midi), L.ptr(offset_cents), window, strength_q, vibrato_q, wild, fold,
+                                 reserved, L.ptr(f0_out), A.vp(k), B, T, T_ph, L.stream_ptr()))
     return (f0_out, k) if return_units else f0_out

@@ -7,6 +7,7 @@ import os
 import torch
 
 from . import _lib as L
+from ._args import vp
 
 
 def _off(t, elems):
@@ -418,7 +419,7 @@ def rel_attention(qkv, n_heads, rel_k=None, rel_v=None, mask=None, window_size=N
                  L.ptr(None if rel_v is None else rel_v.detach().contiguous()), L.ptr(mask), L.ptr(out),
                  C * T, B, n_heads, C // n_heads, T, ws, 1 if rel_k is None else rel_k.shape[0],
                  int(math), L.ptr(work), ksplit,
-                 None if kv_work is None else ctypes.c_void_p(kv_work.data_ptr()), kv_bytes, L.stream_ptr())
+                 vp(kv_work), kv_bytes, L.stream_ptr())
     if ev:      # algorithmic work: Q K^T and P V over the full [T, T] score matrix = 4 * T * T * k_channels per head
         PROFILER.records.append((lib.vs_last_kernel_name().decode(), 4.0 * B * C * T * T, 4.0 * B * 4 * C * T) + ev)
     return out
@@ -442,7 +443,7 @@ def layernorm_c(a, gamma, beta, r=None, g=None, mask=None, eps=1e-4, out=None):
 def _i64ptr(t):
     if not (t.is_cuda and t.dtype == torch.int64 and t.is_contiguous()):
         raise L.VisingerHipError("expected a contiguous int64 tensor on the GPU")
-    return ctypes.c_void_p(t.data_ptr())
+    return vp(t)
 
 
 def expand_states(h, mel2token, h_channels_first=False, out_channels_first=False):
@@ -464,7 +465,7 @@ def make_positions(x, padding_idx):
     x = x.contiguous().float()
     B, T = x.shape
     pos = torch.empty((B, T), device=x.device, dtype=torch.int64)
-    L.check(lib.vs_make_positions(L.ptr(x), ctypes.c_void_p(pos.data_ptr()), B, T, int(padding_idx), L.stream_ptr()))
+    L.check(lib.vs_make_positions(L.ptr(x), vp(pos), B, T, int(padding_idx), L.stream_ptr()))
     return pos
 
 

@@ -6,12 +6,9 @@ optional transposition in cents per item and the sung curve back in Hz.
 Everything that changes between two calls -- the curve, the lengths, the shifts -- is read from device tensors, never on the host: a captured
 graph replays under another curve or another shift by overwriting those buffers.  GPU tensors only; there is no CPU path and no backward
 (an input that requires grad is refused while autograd records)."""
-import ctypes
-import math
-import numbers
-
 import torch
 
+from . import _args as A
 from . import _lib as L
 
 T_LIMIT = 1 << 24            # vs_f0_norm_interp: frame distances are exact in fp32 below it
@@ -41,31 +38,17 @@ def norm_interp_f0(f0_hz, lengths=None):
     if B == 0 or T == 0 or T >= T_LIMIT:
         raise L.VisingerHipError(f"norm_interp_f0: B, T must be positive and T < 2^24, got {(B, T)}")
     if lengths is not None:
-        if not (torch.is_tensor(lengths) and lengths.is_cuda and lengths.dtype == torch.int64 and tuple(lengths.shape) == (B,)):
-            raise L.VisingerHipError(f"norm_interp_f0: lengths must be an int64 GPU tensor [{B}], got {lengths!r:.80}")
-        lengths = lengths.contiguous()
+        lengths = A.gpu_tensor("norm_interp_f0", "lengths", lengths, torch.int64, (B,))
     lib = L.require_gpu()
     f0_norm, uv = torch.empty_like(f0), torch.empty_like(f0)
-    L.check(lib.vs_f0_norm_interp(L.ptr(f0), None if lengths is None else ctypes.c_void_p(lengths.data_ptr()), L.ptr(f0_norm), L.ptr(uv), B, T,
-                                  L.stream_ptr()))
+    L.check(lib.vs_f0_norm_interp(L.ptr(f0), A.vp(lengths), L.ptr(f0_norm), L.ptr(uv), B, T, L.stream_ptr()))
     return f0_norm, uv
 
 
 def cents_tensor(cents, B, device):
     """fp32 [B] on the device: a number (every item), a sequence of B numbers, or a 1-D fp32 GPU tensor [B] -- used as it is and never read
     back (its values are the caller's to keep finite)."""
-    if torch.is_tensor(cents) and cents.is_cuda:
-        if not (cents.dtype == torch.float32 and tuple(cents.shape) == (B,)):
-            raise L.VisingerHipError(f"pitch_shift_cents as a GPU tensor must be fp32 [{B}], got {cents.dtype} {tuple(cents.shape)}")
-        return cents.contiguous()
-    if torch.is_tensor(cents):
-        cents = cents.tolist()
-    vals = [float(cents)] * B if isinstance(cents, numbers.Real) else [float(c) for c in cents]
-    if len(vals) != B:
-        raise ValueError(f"{len(vals)} pitch shifts for a batch of {B}")
-    if not all(math.isfinite(v) for v in vals):
-        raise ValueError(f"a pitch shift must be a finite number of cents, got {vals}")
-    return torch.tensor(vals, dtype=torch.float32).to(device)
+    return A.per_item_f32("pitch shifts", cents, B, device)
 
 
 def pitch_condition(frame_mask, pred=None, f0_norm=None, uv=None, cents=None, return_hz=False):

@@ -6,12 +6,12 @@ reproduced.  This is YIN (de Cheveigne & Kawahara 2002) with a lag-centred diffe
 Everything that changes between two calls -- the samples, the lengths -- is read from device tensors; with a device ``lengths`` and ``frames=`` nothing
 is read on the host, so a captured graph replays on another recording by overwriting those buffers.  GPU tensors only; there is no CPU path and no
 backward (a recording is data: an input that requires grad is refused while autograd records)."""
-import ctypes
 import math
 import numbers
 
 import torch
 
+from . import _args as A
 from . import _lib as L
 
 TAU_LIMIT = 1024             # vs_f0_yin: ceil(sample_rate / f0_min)
@@ -26,7 +26,7 @@ def lag_range(sample_rate, f0_min, f0_max):
 def check_args(hop_size, sample_rate, f0_min=65.0, f0_max=1000.0, window=None, threshold=0.15, silence=1e-8, frames=None):
     """ValueError for host values vs_f0_yin would refuse; returns the window W"""
     for name, v in (("hop_size", hop_size), ("sample_rate", sample_rate)):
-        if not (isinstance(v, numbers.Integral) and not isinstance(v, bool) and 1 <= v < 1 << 31):
+        if not A.is_int(v, 1, (1 << 31) - 1):
             raise ValueError(f"{name} must be an integer >= 1, got {v!r}")
     for name, v in (("f0_min", f0_min), ("f0_max", f0_max), ("threshold", threshold)):
         if not (isinstance(v, numbers.Real) and math.isfinite(v) and v > 0):
@@ -38,7 +38,7 @@ def check_args(hop_size, sample_rate, f0_min=65.0, f0_max=1000.0, window=None, t
     tau_min, tau_max = lag_range(sample_rate, f0_min, f0_max)
     if tau_max > TAU_LIMIT or tau_min >= tau_max:
         raise ValueError(f"the lag range [{tau_min}, {tau_max}] of {f0_min} .. {f0_max} Hz at {sample_rate} Hz must be non-empty and end at or below {TAU_LIMIT}")
-    if window is not None and not (isinstance(window, numbers.Integral) and tau_max <= window <= WINDOW_LIMIT):
+    if window is not None and not A.is_int(window, tau_max, WINDOW_LIMIT):
         raise ValueError(f"window must be an integer in [tau_max = {tau_max}, {WINDOW_LIMIT}], got {window!r}")
     W = 2 * tau_max if window is None else int(window)
     if W > WINDOW_LIMIT:
@@ -67,21 +67,13 @@ def extract_f0(wav, hop_size, sample_rate, f0_min=65.0, f0_max=1000.0, lengths=N
     B, n = wav.shape
     if B == 0 or n == 0 or n >= 1 << 31:
         raise L.VisingerHipError(f"extract_f0: B > 0 and 0 < L < 2^31 are required, got {(B, n)}")
-    if torch.is_tensor(lengths) and lengths.is_cuda:
-        if not (lengths.dtype == torch.int64 and tuple(lengths.shape) == (B,)):
-            raise L.VisingerHipError(f"extract_f0: lengths as a GPU tensor must be int64 [{B}], got {lengths.dtype} {tuple(lengths.shape)}")
-        lengths = lengths.contiguous()
-    elif lengths is not None:
-        vals = [int(v) for v in (lengths.tolist() if torch.is_tensor(lengths) else lengths)]
-        if len(vals) != B or not all(0 <= v <= n for v in vals):
-            raise ValueError(f"lengths must be {B} integers in [0, {n}], got {vals if len(vals) <= 8 else vals[:8] + ['...']}")
-        lengths = torch.tensor(vals, dtype=torch.int64).to(wav.device)
+    lengths = A.lengths_i64("extract_f0", "lengths", lengths, B, n, wav.device)
     T = n // int(hop_size) if frames is None else int(frames)
     if T < 1:
         raise ValueError(f"a recording of {n} samples has no frame of {hop_size}: give at least hop_size samples (or frames=)")
     lib = L.require_gpu()
     f0 = torch.empty((B, T), device=wav.device, dtype=torch.float32)
     per = torch.empty_like(f0) if return_periodicity else None
-    L.check(lib.vs_f0_yin(L.ptr(wav), None if lengths is None else ctypes.c_void_p(lengths.data_ptr()), B, n, int(sample_rate), int(hop_size), float(f0_min),
+    L.check(lib.vs_f0_yin(L.ptr(wav), A.vp(lengths), B, n, int(sample_rate), int(hop_size), float(f0_min),
                           float(f0_max), 0 if window is None else int(window), float(threshold), float(silence), L.ptr(f0), L.ptr(per), T, L.stream_ptr()))
     return (f0, per) if return_periodicity else f0

@@ -6,11 +6,10 @@ The stream (DESIGN.md "Seeded sampling"): Philox4x32-10 keyed by the item seed, 
 pairs per call.  ``seeds`` is one integer in [0, 2^63) per item: a sequence of Python ints (checked here, copied to the device) or an
 int64 CUDA tensor [B] (used as it is and never read back: no host synchronisation, so a captured graph replays with whatever the buffer
 holds; its values are the caller's to keep in range)."""
-import ctypes
-
 import torch
 
 from . import _lib as L
+from ._args import vp
 
 SEED_LIMIT = 1 << 63
 TAKE_LIMIT = 1 << 32
@@ -56,7 +55,7 @@ def item_noise(seeds, H, T, takes=1, first_take=0, device=None):
     sd = seeds_tensor(seeds, device)
     lib = L.require_gpu()
     out = torch.empty((sd.shape[0] * takes, int(H), int(T)), device=sd.device, dtype=torch.float32)
-    L.check(lib.vs_normal_fill(ctypes.c_void_p(sd.data_ptr()), first_take, takes, L.ptr(out), sd.shape[0], int(H), int(T), L.stream_ptr()))
+    L.check(lib.vs_normal_fill(vp(sd), first_take, takes, L.ptr(out), sd.shape[0], int(H), int(T), L.stream_ptr()))
     return out
 
 
@@ -96,7 +95,7 @@ def prior_sample(mu_p, logs_p, frame_mask, seeds, takes=1, first_take=0, noise_s
         mask = frame_mask.reshape(B, T).float().contiguous()
     z = torch.empty((B * takes, H, T), device=mu.device, dtype=torch.float32)
     eps = torch.empty_like(z) if return_noise else None
-    L.check(lib.vs_prior_sample(ctypes.c_void_p(mu.data_ptr()), ctypes.c_void_p(logs.data_ptr()), bs, L.ptr(mask), ctypes.c_void_p(sd.data_ptr()),
+    L.check(lib.vs_prior_sample(vp(mu), vp(logs), bs, L.ptr(mask), vp(sd),
                                 first_take, takes, float(noise_scale), L.ptr(z), L.ptr(eps), B, H, T, L.stream_ptr()))
     if z.dtype != mu_p.dtype:
         z = z.to(mu_p.dtype)

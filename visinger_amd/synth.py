@@ -28,6 +28,21 @@ def bucket_by_length(lengths, max_frames_per_batch, max_items_per_batch=256, key
     return batches
 
 
+def _buckets(lengths, max_frames_per_batch):
+    """bucket_by_length over {item index: length}: lists of item indices"""
+    order = list(lengths)
+    for idx in bucket_by_length([lengths[i] for i in order], max_frames_per_batch):
+        yield [order[j] for j in idx]
+
+
+def _pad_rows(rows, dtype, width=None, fill=0):
+    """host tensor [len(rows), width] (default: the longest row) whose row b begins with a copy of rows[b]; the rest is `fill`"""
+    out = torch.full((len(rows), max(len(r) for r in rows) if width is None else width), fill, dtype=dtype)
+    for b, r in enumerate(rows):
+        out[b, :len(r)] = torch.as_tensor(np.asarray(r), dtype=dtype)
+    return out
+
+
 def collate(items, device):
     """items: dicts with int64 1-D arrays text_tokens, pitch_tokens, dur_tokens (T_ph) and mel2ph (T_mel); 0-padded.
     An item may carry "f0": a guide curve in Hz, one value per frame of its mel2ph (0 = unvoiced) -> batch["f0_hz"], fp32 [B, T_mel], padded
@@ -37,20 +52,14 @@ def collate(items, device):
         raise ValueError("items with and without a guide curve ('f0') cannot share a batch")
     Tph = max(len(it["text_tokens"]) for it in items)
     T = max(len(it["mel2ph"]) for it in items)
-    out = {k: torch.zeros((len(items), Tph if k != "mel2ph" else T), dtype=torch.long)
+    out = {k: _pad_rows([it[k] for it in items], torch.long, Tph if k != "mel2ph" else T)
            for k in ("text_tokens", "pitch_tokens", "dur_tokens", "mel2ph")}
-    for b, it in enumerate(items):
-        for k in out:
-            v = torch.as_tensor(np.asarray(it[k]), dtype=torch.long)
-            out[k][b, :len(v)] = v
     out["spk_id"] = torch.as_tensor([int(it.get("spk_id", 0)) for it in items], dtype=torch.long)
     if guided and guided[0]:
-        out["f0_hz"] = torch.zeros((len(items), T), dtype=torch.float32)
         for b, it in enumerate(items):
-            v = torch.as_tensor(np.asarray(it["f0"], dtype=np.float32))
-            if v.dim() != 1 or len(v) != len(it["mel2ph"]):
-                raise ValueError(f"item {b}: the guide curve has {tuple(v.shape)} values for {len(it['mel2ph'])} frames (one value in Hz per frame)")
-            out["f0_hz"][b, :len(v)] = v
+            if np.shape(it["f0"]) != (len(it["mel2ph"]),):
+                raise ValueError(f"item {b}: the guide curve has {np.shape(it['f0'])} values for {len(it['mel2ph'])} frames (one value in Hz per frame)")
+        out["f0_hz"] = _pad_rows([it["f0"] for it in items], torch.float32, T)
     return {k: v.to(device) for k, v in out.items()}
 
 
@@ -130,6 +139,20 @@ class GraphedStep:
         through `.data`, like the packed-weight caches: call hipconv.repack_weights AND drop the graphs after such an edit)"""
         return tuple((p.data_ptr(), p._version) for p in model.parameters())
 
+    # the optional static control buffers: attribute -> the device tensor of a value, for a step of B items of T_ph tokens
+    CONTROLS = dict(seeds=lambda v, B, T_ph, dev: sampling.seeds_tensor(v), cents=lambda v, B, T_ph, dev: pitch.cents_tensor(v, B, dev),
+                    tempo=lambda v, B, T_ph, dev: timing.factor_tensor(v, B, dev), ph_stretch=timing.stretch_tensor)
+    # what a replay is told whose optional inputs are not the capture's, in the order they are compared
+    _SAMPLE = "a graph captured with noise is replayed with noise, one captured with seeds with seeds"
+    _PITCH = "a graph is replayed with the inputs it was captured with (guide curve and pitch shift included)"
+    _TEMPO = "a graph captured with a tempo / token stretch is replayed with one (and one captured without, without)"
+    REFUSALS = dict(seeds=_SAMPLE, noise=_SAMPLE, f0_hz=_PITCH, cents=_PITCH, tempo=_TEMPO, ph_stretch=_TEMPO)
+
+    def _controls(self, **given):
+        """{attribute: device tensor, or None where no value is given}"""
+        size = (self.static["mel2ph"].shape[0], self.static["text_tokens"].shape[1], self.static["mel2ph"].device)
+        return {k: None if given[k] is None else make(given[k], *size) for k, make in self.CONTROLS.items()}
+
     def __init__(self, model, batch, noise, mask_decoder, seeds=None, takes=1, first_take=0, noise_scale=1.0, voicing="guide", cents=None, tempo=None,
                  ph_stretch=None, max_frames=None):
         if seeds is not None and noise is not None:
@@ -139,16 +162,12 @@ class GraphedStep:
         self.weights = self.fingerprint(model)       # a replay never re-folds / re-packs weights: the graph is only valid for these
         self.static = {k: v.clone() for k, v in batch.items()}
         self.noise = None if seeds is not None else noise.clone()
-        self.seeds = None if seeds is None else sampling.seeds_tensor(seeds).clone()
+        for k, t in self._controls(seeds=seeds, cents=cents, tempo=tempo, ph_stretch=ph_stretch).items():
+            setattr(self, k, None if t is None else t.clone())
         sample = dict(noise=self.noise) if seeds is None else dict(seeds=self.seeds, takes=takes, first_take=first_take, noise_scale=noise_scale)
-        self.cents = None if cents is None else pitch.cents_tensor(cents, batch["mel2ph"].shape[0], batch["mel2ph"].device).clone()
-        self.f0_hz_out = None
+        self.f0_hz_out = self.frame_lengths_out = self.mel2ph_out = None
         if "f0_hz" in batch or self.cents is not None:
             sample.update(f0_hz=self.static.get("f0_hz"), voicing=voicing, pitch_shift_cents=self.cents)
-        B, dev = batch["mel2ph"].shape[0], batch["mel2ph"].device
-        self.tempo = None if tempo is None else timing.factor_tensor(tempo, B, dev).clone()
-        self.ph_stretch = None if ph_stretch is None else timing.stretch_tensor(ph_stretch, B, batch["text_tokens"].shape[1], dev).clone()
-        self.frame_lengths_out = self.mel2ph_out = None
         if max_frames is not None:
             sample.update(tempo=self.tempo, ph_stretch=self.ph_stretch, max_frames=int(max_frames))
 
@@ -170,24 +189,17 @@ class GraphedStep:
             self.out = run()
 
     def __call__(self, batch, noise, seeds=None, cents=None, tempo=None, ph_stretch=None):
-        if (self.seeds is None) != (seeds is None) or (self.noise is None) != (noise is None):
-            raise ValueError("a graph captured with noise is replayed with noise, one captured with seeds with seeds")
-        if ("f0_hz" in batch) != ("f0_hz" in self.static) or (self.cents is None) != (cents is None):
-            raise ValueError("a graph is replayed with the inputs it was captured with (guide curve and pitch shift included)")
-        if (self.tempo is None) != (tempo is None) or (self.ph_stretch is None) != (ph_stretch is None):
-            raise ValueError("a graph captured with a tempo / token stretch is replayed with one (and one captured without, without)")
+        given = dict(noise=noise, f0_hz=batch.get("f0_hz"), seeds=seeds, cents=cents, tempo=tempo, ph_stretch=ph_stretch)
+        for k, refusal in self.REFUSALS.items():
+            if (given[k] is None) != ((self.static.get(k) if k == "f0_hz" else getattr(self, k)) is None):
+                raise ValueError(refusal)
         for k, v in batch.items():
             self.static[k].copy_(v)
-        if self.tempo is not None:
-            self.tempo.copy_(timing.factor_tensor(tempo, self.tempo.shape[0], self.tempo.device))
-        if self.ph_stretch is not None:
-            self.ph_stretch.copy_(timing.stretch_tensor(ph_stretch, *self.ph_stretch.shape, self.ph_stretch.device))
-        if self.cents is not None:
-            self.cents.copy_(pitch.cents_tensor(cents, self.cents.shape[0], self.cents.device))
-        if self.seeds is not None:
-            self.seeds.copy_(seeds)
-        else:
+        if noise is not None:
             self.noise.copy_(noise)
+        for k, t in self._controls(**given).items():
+            if t is not None:
+                getattr(self, k).copy_(t)
         self.graph.replay()
         return self.out          # the graph's STATIC output buffer: the next replay overwrites it (clone to keep it)
 
@@ -214,13 +226,8 @@ def guide_items(items, hop_size, device, max_frames_per_batch=32768, fit=True, *
             raise ValueError(f"item {i}: guide_wav must be a 1-D float array of at least hop_size = {hop_size} samples, got {w.dtype} {w.shape}")
         wavs[i] = w.astype(np.float32, copy=False)
     out = [dict(it) for it in items]
-    order = list(wavs)
-    for idx in bucket_by_length([len(wavs[i]) // hop_size for i in order], max_frames_per_batch):
-        idx = [order[j] for j in idx]
-        n = max(len(wavs[i]) for i in idx)
-        wav = torch.zeros((len(idx), n), dtype=torch.float32)
-        for b, i in enumerate(idx):
-            wav[b, :len(wavs[i])] = torch.from_numpy(wavs[i])
+    for idx in _buckets({i: len(w) // hop_size for i, w in wavs.items()}, max_frames_per_batch):
+        wav = _pad_rows([wavs[i] for i in idx], torch.float32)
         lens = torch.tensor([len(wavs[i]) for i in idx], dtype=torch.int64).to(device)
         f0 = pitch_track.extract_f0(wav.to(device), hop_size, lengths=lens, **track).cpu().numpy()
         for b, i in enumerate(idx):
@@ -231,6 +238,32 @@ def guide_items(items, hop_size, device, max_frames_per_batch=32768, fit=True, *
             del out[i]["guide_wav"]
             out[i]["f0"] = curve
     return out
+
+
+def _token_pitches(items, table, curve_of):
+    """({i: note_midi}, {i: curve}, {i: the item's own "guide_offset_cents" or None}) of the items that carry a guide curve "f0" and token pitches: "note_midi",
+    or "pitch_tokens" through `table` (midi_of_token).  curve_of(i, item, n_tok) returns the item's checked curve.  A ValueError names the item."""
+    table = None if table is None else np.asarray(table, dtype=np.float32)
+    if table is not None and table.ndim != 1:
+        raise ValueError(f"midi_of_token must be a 1-D sequence of MIDI numbers indexed by pitch token, got shape {table.shape}")
+    notes, curves, offsets = {}, {}, {}
+    for i, it in enumerate(items):
+        if it.get("f0") is None or (it.get("note_midi") is None and table is None):
+            continue
+        n_tok = len(it["text_tokens"])
+        if it.get("note_midi") is not None:
+            nm = np.asarray(it["note_midi"], dtype=np.float32)
+            if nm.shape != (n_tok,):
+                raise ValueError(f"item {i}: note_midi has shape {nm.shape} for {n_tok} tokens (one MIDI number per token)")
+        else:
+            pt = np.asarray(it["pitch_tokens"]).astype(np.int64)
+            if pt.shape != (n_tok,) or (pt < 0).any() or (pt >= len(table)).any():
+                raise ValueError(f"item {i}: pitch_tokens must be {n_tok} ids in [0, {len(table)}) to go through midi_of_token")
+            nm = table[pt]
+        notes[i], curves[i], offsets[i] = nm, curve_of(i, it, n_tok), it.get("guide_offset_cents")
+        if offsets[i] is not None and not (isinstance(offsets[i], (int, float)) and abs(offsets[i]) < float("inf")):
+            raise ValueError(f"item {i}: guide_offset_cents must be a finite number, got {offsets[i]!r}")
+    return notes, curves, offsets
 
 
 def align_items(items, device, max_frames_per_batch=32768, **guide_align):
@@ -250,40 +283,19 @@ def align_items(items, device, max_frames_per_batch=32768, **guide_align):
     guide_align_ops.check_args(**guide_align)
     if not (isinstance(offset, (int, float)) and abs(offset) < float("inf")):
         raise ValueError(f"offset_cents must be a finite number, got {offset!r}")
-    table = None if table is None else np.asarray(table, dtype=np.float32)
-    if table is not None and table.ndim != 1:
-        raise ValueError(f"midi_of_token must be a 1-D sequence of MIDI numbers indexed by pitch token, got shape {table.shape}")
-    out = [dict(it) for it in items]
-    notes, curves = {}, {}
-    for i, it in enumerate(items):
-        if it.get("f0") is None or (it.get("note_midi") is None and table is None):
-            continue
-        n_tok = len(it["text_tokens"])
-        if it.get("note_midi") is not None:
-            nm = np.asarray(it["note_midi"], dtype=np.float32)
-            if nm.shape != (n_tok,):
-                raise ValueError(f"item {i}: note_midi has shape {nm.shape} for {n_tok} tokens (one MIDI number per token)")
-        else:
-            pt = np.asarray(it["pitch_tokens"]).astype(np.int64)
-            if pt.shape != (n_tok,) or (pt < 0).any() or (pt >= len(table)).any():
-                raise ValueError(f"item {i}: pitch_tokens must be {n_tok} ids in [0, {len(table)}) to go through midi_of_token")
-            nm = table[pt]
+    def curve_of(i, it, n_tok):
         f0 = np.asarray(it["f0"], dtype=np.float32)
         if f0.ndim != 1 or not 1 <= len(f0) <= guide_align_ops.TG_LIMIT or not 1 <= n_tok <= guide_align_ops.T_PH_LIMIT:
             raise ValueError(f"item {i}: a guide curve of 1 .. {guide_align_ops.TG_LIMIT} frames (1-D) and 1 .. {guide_align_ops.T_PH_LIMIT} tokens can be aligned, "
                              f"got {f0.shape} and {n_tok}")
-        notes[i], curves[i] = nm, f0
-    order = list(notes)
-    for idx in bucket_by_length([len(curves[i]) for i in order], max_frames_per_batch):
-        idx = [order[j] for j in idx]
-        B, Tg = len(idx), max(len(curves[i]) for i in idx)
-        T_ph, T = max(len(notes[i]) for i in idx), max(1, max(len(items[i]["mel2ph"]) for i in idx))
-        f0, nm = torch.zeros((B, Tg), dtype=torch.float32), torch.zeros((B, T_ph), dtype=torch.float32)
-        m2p = torch.zeros((B, T), dtype=torch.long)
-        for b, i in enumerate(idx):
-            f0[b, :len(curves[i])], nm[b, :len(notes[i])] = torch.from_numpy(curves[i]), torch.from_numpy(notes[i])
-            m2p[b, :len(items[i]["mel2ph"])] = torch.as_tensor(np.asarray(items[i]["mel2ph"]), dtype=torch.long)
-        cents = [float(items[i].get("guide_offset_cents", offset)) for i in idx]
+        return f0
+
+    notes, curves, offsets = _token_pitches(items, table, curve_of)
+    out = [dict(it) for it in items]
+    for idx in _buckets({i: len(f0) for i, f0 in curves.items()}, max_frames_per_batch):
+        f0, nm = _pad_rows([curves[i] for i in idx], torch.float32), _pad_rows([notes[i] for i in idx], torch.float32)
+        m2p = _pad_rows([items[i]["mel2ph"] for i in idx], torch.long, max(1, max(len(items[i]["mel2ph"]) for i in idx)))
+        cents = [float(offset if offsets[i] is None else offsets[i]) for i in idx]
         dur_new, _, status = guide_align_ops.align_guide(f0.to(device), nm.to(device), mel2ph=m2p.to(device), guide_lengths=[len(curves[i]) for i in idx],
                                                          offset_cents=cents, **guide_align)
         status = status.cpu().tolist()
@@ -315,45 +327,22 @@ def correct_items(items, device, max_frames_per_batch=32768, **guide_correct):
     auto = isinstance(offset, str) and offset == "auto"
     if not auto and not (isinstance(offset, (int, float)) and abs(offset) < float("inf")):
         raise ValueError(f"offset_cents must be a finite number or 'auto', got {offset!r}")
-    table = None if table is None else np.asarray(table, dtype=np.float32)
-    if table is not None and table.ndim != 1:
-        raise ValueError(f"midi_of_token must be a 1-D sequence of MIDI numbers indexed by pitch token, got shape {table.shape}")
-    out = [dict(it) for it in items]
-    notes, curves = {}, {}
-    for i, it in enumerate(items):
-        if it.get("f0") is None or (it.get("note_midi") is None and table is None):
-            continue
-        n_tok, n_frames = len(it["text_tokens"]), len(it["mel2ph"])
-        if it.get("note_midi") is not None:
-            nm = np.asarray(it["note_midi"], dtype=np.float32)
-            if nm.shape != (n_tok,):
-                raise ValueError(f"item {i}: note_midi has shape {nm.shape} for {n_tok} tokens (one MIDI number per token)")
-        else:
-            pt = np.asarray(it["pitch_tokens"]).astype(np.int64)
-            if pt.shape != (n_tok,) or (pt < 0).any() or (pt >= len(table)).any():
-                raise ValueError(f"item {i}: pitch_tokens must be {n_tok} ids in [0, {len(table)}) to go through midi_of_token")
-            nm = table[pt]
-        f0 = np.asarray(it["f0"], dtype=np.float32)
+    def curve_of(i, it, n_tok):
+        f0, n_frames = np.asarray(it["f0"], dtype=np.float32), len(it["mel2ph"])
         if f0.shape != (n_frames,):
             raise ValueError(f"item {i}: the guide curve has {f0.shape} values for {n_frames} frames (one value in Hz per frame)")
         if not 1 <= n_frames <= guide_correct_ops.T_LIMIT or not 1 <= n_tok <= guide_correct_ops.T_PH_LIMIT:
             raise ValueError(f"item {i}: a guide curve of 1 .. {guide_correct_ops.T_LIMIT} frames and 1 .. {guide_correct_ops.T_PH_LIMIT} tokens can be "
                              f"corrected, got {n_frames} and {n_tok}")
-        own = it.get("guide_offset_cents")
-        if own is not None and not (isinstance(own, (int, float)) and abs(own) < float("inf")):
-            raise ValueError(f"item {i}: guide_offset_cents must be a finite number, got {own!r}")
-        notes[i], curves[i] = nm, f0
-    order = list(notes)
-    for idx in bucket_by_length([len(curves[i]) for i in order], max_frames_per_batch):
-        idx = [order[j] for j in idx]
-        B, T, T_ph = len(idx), max(len(curves[i]) for i in idx), max(len(notes[i]) for i in idx)
-        f0, nm, m2p = torch.zeros((B, T), dtype=torch.float32), torch.zeros((B, T_ph), dtype=torch.float32), torch.zeros((B, T), dtype=torch.long)
-        for b, i in enumerate(idx):
-            f0[b, :len(curves[i])], nm[b, :len(notes[i])] = torch.from_numpy(curves[i]), torch.from_numpy(notes[i])
-            m2p[b, :len(curves[i])] = torch.as_tensor(np.asarray(items[i]["mel2ph"]), dtype=torch.long)
-        f0, nm, m2p = f0.to(device), nm.to(device), m2p.to(device)
+        return f0
+
+    notes, curves, offsets = _token_pitches(items, table, curve_of)
+    out = [dict(it) for it in items]
+    for idx in _buckets({i: len(f0) for i, f0 in curves.items()}, max_frames_per_batch):
+        f0, nm = _pad_rows([curves[i] for i in idx], torch.float32).to(device), _pad_rows([notes[i] for i in idx], torch.float32).to(device)
+        m2p = _pad_rows([items[i]["mel2ph"] for i in idx], torch.long).to(device)
         lens = [len(curves[i]) for i in idx]
-        own = [items[i].get("guide_offset_cents") for i in idx]
+        own = [offsets[i] for i in idx]
         cents = torch.tensor([float(0.0 if auto else offset) if v is None else float(v) for v in own], dtype=torch.float32).to(device)
         if auto and any(v is None for v in own):                         # the key of every item that does not bring its own, never read back
             med, _ = guide_correct_ops.guide_deviation(f0, m2p, nm, lengths=lens, wild_cents=guide_correct.get("wild_cents", 300.0),
@@ -385,16 +374,10 @@ def retime_items(items, tempo, device, max_frames_per_batch=32768):
     out = [None] * n
     guided = [it.get("f0") is not None for it in items]
     for idx in bucket_by_length([len(it["mel2ph"]) for it in items], max_frames_per_batch, keys=guided):
-        B, T = len(idx), max(1, max(len(items[i]["mel2ph"]) for i in idx))
-        T_ph = max(len(items[i]["text_tokens"]) for i in idx)
-        m2p, st = torch.zeros((B, T), dtype=torch.long), torch.ones((B, T_ph), dtype=torch.float32)
-        curve = torch.zeros((B, T), dtype=torch.float32) if guided[idx[0]] else None
-        for b, i in enumerate(idx):
-            m2p[b, :len(items[i]["mel2ph"])] = torch.as_tensor(np.asarray(items[i]["mel2ph"]), dtype=torch.long)
-            st[b, :len(stretches[i])] = torch.from_numpy(stretches[i])
-            if curve is not None:
-                curve[b, :len(items[i]["f0"])] = torch.as_tensor(np.asarray(items[i]["f0"], dtype=np.float32))
-        new, lens, warped = timing.retime(mel2ph=m2p.to(device), T_ph=T_ph, stretch=st.to(device), tempo=[tempos[i] for i in idx],
+        T = max(1, max(len(items[i]["mel2ph"]) for i in idx))
+        m2p, st = _pad_rows([items[i]["mel2ph"] for i in idx], torch.long, T), _pad_rows([stretches[i] for i in idx], torch.float32, fill=1)
+        curve = _pad_rows([items[i]["f0"] for i in idx], torch.float32, T) if guided[idx[0]] else None
+        new, lens, warped = timing.retime(mel2ph=m2p.to(device), T_ph=st.shape[1], stretch=st.to(device), tempo=[tempos[i] for i in idx],
                                           curve=None if curve is None else curve.to(device))
         new, lens = new.cpu().numpy(), lens.cpu().tolist()
         warped = None if warped is None else warped.cpu().numpy()
@@ -470,16 +453,17 @@ def synthesize(model, items, hop_size, max_frames_per_batch=32768, noise_scale=1
         raise ValueError(f"guide_correct must be a dict of correct_items keywords (possibly empty) or None, got {guide_correct!r:.60}")
     if guide_align is not None and not isinstance(guide_align, dict):
         raise ValueError(f"guide_align must be a dict of align_items keywords (possibly empty) or None, got {guide_align!r:.60}")
+    device = next(model.parameters()).device
     if any(it.get("guide_wav") is not None for it in items):
         if guide_track is None or "sample_rate" not in guide_track:
             raise ValueError("an item carries 'guide_wav': give guide_track, a dict of pitch_track.extract_f0 keywords with sample_rate")
-        items = guide_items(items, hop_size, next(model.parameters()).device, max_frames_per_batch, fit=guide_align is None, **guide_track)
+        items = guide_items(items, hop_size, device, max_frames_per_batch, fit=guide_align is None, **guide_track)
     if guide_align is not None:
-        items = align_items(items, next(model.parameters()).device, max_frames_per_batch, **guide_align)
+        items = align_items(items, device, max_frames_per_batch, **guide_align)
     if guide_correct is not None:
-        items = correct_items(items, next(model.parameters()).device, max_frames_per_batch, **guide_correct)
+        items = correct_items(items, device, max_frames_per_batch, **guide_correct)
     if tempo is not None or any(it.get("ph_stretch") is not None for it in items):
-        items = retime_items(items, tempo, next(model.parameters()).device, max_frames_per_batch)
+        items = retime_items(items, tempo, device, max_frames_per_batch)
     if voicing not in ("guide", "model"):
         raise ValueError(f"voicing must be 'guide' or 'model', got {voicing!r}")
     if pitch_shift_cents is not None:
@@ -496,7 +480,6 @@ def synthesize(model, items, hop_size, max_frames_per_batch=32768, noise_scale=1
         takes, first_take = sampling.check_takes(takes, first_take)
     elif takes != 1 or first_take != 0:
         raise ValueError("takes / first_take select samples of the seeded streams: give seeds")
-    device = next(model.parameters()).device
     lengths = [int((np.asarray(it["mel2ph"]) > 0).sum()) for it in items]
     out = [None] * len(items)
     guided = ["f0" in it and it["f0"] is not None for it in items]

@@ -11,59 +11,33 @@ The rule (include/visinger_hip.h "f5"): d_i = frames of token i, s_i = rint(clam
 e_i = max(e_{i-1} + (d_i > 0 ? min_frames : 0), (sum_{j<=i} d_j s_j + 32768) >> 16): cumulative rounding, so the total never drifts from the
 exact product by more than half a frame, and a token that had frames keeps min_frames of them however fast the tempo.  The alignment must be
 monotonic over its valid prefix, as get_note2dur always produces it (not checked on the device)."""
-import ctypes
 import math
-import numbers
 
 import torch
 
+from . import _args as A
 from . import _lib as L
 
 T_FRAMES_LIMIT = 1 << 24     # vs_retime_tokens: frames of the old alignment
 T_TOKENS_LIMIT = 8192        # ... and tokens (its LDS histogram)
 
 
-def _i64(name, t, B=None):
-    if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.int64 and t.dim() == 2 and (B is None or t.shape[0] == B)):
-        raise L.VisingerHipError(f"{name} must be an int64 [B, T] tensor on the GPU (there is no CPU path), got {t!r:.80}")
-    return t.contiguous()
-
-
-def _vp(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
-
-
-def _host_factors(name, vals):
-    if not all(math.isfinite(v) and v > 0 for v in vals):
-        raise ValueError(f"a {name} must be a finite number > 0, got {vals if len(vals) <= 8 else vals[:8] + ['...']}")
-    return vals
-
-
 def factor_tensor(tempo, B, device):
     """fp32 [B] on the device: a number (every item), a sequence of B numbers, or a 1-D fp32 GPU tensor [B] -- used as it is and never read back
     (the kernel treats a value that gives a non-finite factor as 1 and clamps the factor to [1/64, 64]).  Host values must be finite and > 0."""
-    if torch.is_tensor(tempo) and tempo.is_cuda:
-        if not (tempo.dtype == torch.float32 and tuple(tempo.shape) == (B,)):
-            raise L.VisingerHipError(f"tempo as a GPU tensor must be fp32 [{B}], got {tempo.dtype} {tuple(tempo.shape)}")
-        return tempo.contiguous()
-    if torch.is_tensor(tempo):
-        tempo = tempo.tolist()
-    vals = [float(tempo)] * B if isinstance(tempo, numbers.Real) else [float(v) for v in tempo]
-    if len(vals) != B:
-        raise ValueError(f"{len(vals)} tempos for a batch of {B}")
-    return torch.tensor(_host_factors("tempo", vals), dtype=torch.float32).to(device)
+    return A.per_item_f32("tempos", tempo, B, device, positive=True)
 
 
 def stretch_tensor(stretch, B, T_ph, device):
     """fp32 [B, T_ph] on the device: an fp32 GPU tensor of that shape (used as it is, never read back), or host values [B, T_ph] (finite, > 0)"""
     if torch.is_tensor(stretch) and stretch.is_cuda:
-        if not (stretch.dtype == torch.float32 and tuple(stretch.shape) == (B, T_ph)):
-            raise L.VisingerHipError(f"ph_stretch as a GPU tensor must be fp32 [{B}, {T_ph}], got {stretch.dtype} {tuple(stretch.shape)}")
-        return stretch.contiguous()
+        return A.gpu_tensor("retime", "ph_stretch", stretch, torch.float32, (B, T_ph))
     t = torch.as_tensor(stretch, dtype=torch.float32)
     if tuple(t.shape) != (B, T_ph):
         raise ValueError(f"ph_stretch has shape {tuple(t.shape)} for {B} items of {T_ph} tokens (one factor per token)")
-    _host_factors("stretch factor", t.flatten().tolist())
+    vals = t.flatten().tolist()
+    if not all(math.isfinite(v) and v > 0 for v in vals):
+        raise ValueError(f"a stretch factor must be a finite number > 0, got {A.short(vals)}")
     return t.to(device)
 
 
@@ -78,7 +52,7 @@ def retime(mel2ph=None, dur=None, T_ph=None, stretch=None, tempo=None, min_frame
     Returns mel2ph' int64 [B, T'], lengths int64 [B] (on the device) and curve' fp32 [B, T'] (None without a curve)."""
     if (mel2ph is None) == (dur is None):
         raise L.VisingerHipError("retime: give exactly one of mel2ph and dur")
-    src = _i64("mel2ph" if dur is None else "dur", mel2ph if dur is None else dur)
+    src = A.gpu_tensor("retime", "mel2ph" if dur is None else "dur", mel2ph if dur is None else dur, torch.int64, (None, None))
     B = src.shape[0]
     if dur is not None:
         if T_ph is not None and T_ph != src.shape[1]:
@@ -105,13 +79,13 @@ def retime(mel2ph=None, dur=None, T_ph=None, stretch=None, tempo=None, min_frame
     lib = L.require_gpu()
     cum_old = torch.empty((B, T_ph), device=dev, dtype=torch.int64)
     cum_new, lengths = torch.empty_like(cum_old), torch.empty((B,), device=dev, dtype=torch.int64)
-    L.check(lib.vs_retime_tokens(_vp(src) if dur is None else None, _vp(src) if dur is not None else None, L.ptr(stretch), L.ptr(tempo),
-                                 int(min_frames), 0 if max_frames is None else int(max_frames), _vp(cum_old), _vp(cum_new), _vp(lengths), B, T_frames,
+    L.check(lib.vs_retime_tokens(A.vp(src) if dur is None else None, A.vp(src) if dur is not None else None, L.ptr(stretch), L.ptr(tempo),
+                                 int(min_frames), 0 if max_frames is None else int(max_frames), A.vp(cum_old), A.vp(cum_new), A.vp(lengths), B, T_frames,
                                  T_ph, L.stream_ptr()))
     T_out = int(lengths.max()) if max_frames is None else int(max_frames)        # (None: the one synchronisation)
     out = torch.empty((B, T_out), device=dev, dtype=torch.int64)
     curve_out = None if curve is None else torch.empty((B, T_out), device=dev, dtype=torch.float32)
     if T_out > 0:
-        L.check(lib.vs_retime_frames(_vp(cum_old), _vp(cum_new), _vp(lengths), L.ptr(curve), 0 if curve is None else curve.shape[1], _vp(out),
+        L.check(lib.vs_retime_frames(A.vp(cum_old), A.vp(cum_new), A.vp(lengths), L.ptr(curve), 0 if curve is None else curve.shape[1], A.vp(out),
                                      L.ptr(curve_out), B, T_ph, T_out, L.stream_ptr()))
     return out, lengths, curve_out
