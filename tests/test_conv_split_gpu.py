@@ -193,7 +193,8 @@ def test_split_attention_is_fp32_class(oracle, dk, nh, T, ws, share, math):
     probabilities split exactly into three bf16 planes, six cross products per product) and VS_MATH_SPLIT3 (TERMS = 3, the default
     arithmetic of the path since round 6: two f16 planes under power-of-two scales -- per query, per K tile, running per V tile -- three
     cross products) -- against the exact-fp32 MFMA kernel AND the fp64 restatement (rel_transformer.py:148-179): fp32-class agreement,
-    the same bar the fp32 kernel is held to."""
+    the same bar the fp32 kernel is held to.  (2e-5 is a hundred times these kernels' own error: the element-wise bound, against the fp64 sums of
+    the device's own operand planes, is tests/test_attention_split3_oracle_gpu.py.)"""
     from visinger_amd.ops import rel_attention
     from visinger_amd import _lib
     g = torch.Generator().manual_seed(dk * 11 + T)
@@ -223,7 +224,8 @@ def test_split_f16_attention_scales_follow_the_data(case):
     grow or shrink by 2^24 along the sequence (every K tile under its own scale; the V scale runs upwards and the output accumulators are
     rescaled when a tile raises it), per-channel gains over 2^-8 .. 2^8, single keys 2^12 above their neighbours, inputs near 2^-60 and
     near 2^40 (far outside the f16 range without the scales).  Bar: the fp32 MFMA kernel's own error against the fp64 restatement, three
-    times over, relative to the largest output of the (batch, head)."""
+    times over, relative to the largest output of the (batch, head).  (The same six inputs and five more -- zero tiles, a zero query, lane halves,
+    masked outliers, an ev jump -- element by element, with and without the key split: tests/test_attention_split3_oracle_gpu.py.)"""
     from visinger_amd.ops import rel_attention
     from visinger_amd import _lib
     dk, nh, T, ws, B = 96, 2, 516, 4, 2
