@@ -85,6 +85,13 @@ def test_single_frame_1x1_conv(oracle, vs_option, Cin, Cout, B, with_bias):
     x2 = r.standard_normal((B, Cin, 2)).astype(np.float32)
     y2 = op.forward(dev(x2))
     assert op.kernel_instance() != "conv_t1_kernel" and rel_rms(y2, oracle.conv1d(x2.astype(np.float64), w, bias)) <= 3e-6
+    # a PADDED 1 x 1 conv over one frame has 1 + 2 * pad output frames (the padded ones hold the bias alone): not the single-frame kernel's case
+    op_pad = ConvOp(L.CONV1D, Cin, Cout, 1, 1, 1)
+    op_pad.set_weights(dev(w), None, None if bias is None else dev(bias))
+    y_pad = op_pad.forward(dev(x))
+    assert op_pad.kernel_instance() != "conv_t1_kernel"
+    assert y_pad.shape == (B, Cout, 3)
+    assert rel_rms(y_pad, oracle.conv1d(x.astype(np.float64), w, bias, padding=1)) <= 3e-6
 
 
 def test_split_kernel_instances_and_repack(oracle):

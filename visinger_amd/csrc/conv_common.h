@@ -1,5 +1,5 @@
 // conv_common.h -- launch parameters and device helpers shared by the conv kernels of libvisinger_hip.so
-// (conv_engine.hip: fp32 MFMA + Winograd F(2,3); conv_split.hip: split-bf16 MFMA).
+// (conv_engine.hip: fp32 MFMA; conv_wino.hip: Winograd F(2,3); conv_small.hip: VALU and single-frame; conv_split.hip: split-bf16 MFMA).
 #pragma once
 #include "vs_internal.h"
 
@@ -204,5 +204,17 @@ bool ktap_pair_instance(int terms, int kt, int io, int in_act, int mt);      // 
 int launch_ktap_pair(const ConvParams &p, int terms, hipStream_t s);
 bool ktap_tr_instance(const ConvParams &p, int terms, int cfg);               // conv_ktap.hip: VS_CONV_TRANSPOSE1D with two taps per phase (k = 2 * stride), the 128 x 256 tile, split-f16 on fp32 tensors
 int launch_ktap_tr(const ConvParams &p, hipStream_t s);
+
+// ---- the routes of vs_conv_forward (conv_engine.hip) that live in units of their own; p as vs_conv_forward fills it
+static inline bool al16(const void *q) { return (reinterpret_cast<uintptr_t>(q) & 15u) == 0; }   // the vector loads / stores want 16-byte rows
+// conv_small.hip: the VALU kernel for convs with <= 4 output channels, and the 1 x 1 conv over a single frame per item
+bool small_conv_applies(const vs_conv *h, const ConvParams &p);
+int launch_small_conv(const vs_conv *h, const ConvParams &p, hipStream_t s);
+bool t1_conv_applies(const vs_conv *h, const ConvParams &p);
+int launch_t1_conv(const vs_conv *h, const ConvParams &p, hipStream_t s);
+// conv_pack.hip: the F(2,3) transform of the handle's current fp32 fragments into h->wpw, made by the first launch that needs it
+int pack_wino_weights(vs_conv *h, hipStream_t s);
+// conv_wino.hip: the F(2,3) kernel on a handle with wino_groups, after pack_wino_weights
+int launch_wino_conv(const vs_conv *h, const ConvParams &p, hipStream_t s);
 
 }  // namespace vs

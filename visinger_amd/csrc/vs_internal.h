@@ -101,8 +101,8 @@ static inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
 }  // namespace vs
 
-// The conv handle of the C ABI (vs_conv_t), shared by conv_engine.hip (which owns it) and resblock_pair.hip (which runs two
-// of them in one launch).
+// The conv handle of the C ABI (vs_conv_t), shared by conv_engine.hip (which owns it), conv_pack.hip (which binds its weights), the
+// launchers of conv_small.hip / conv_wino.hip and resblock_pair.hip (which runs two of them in one launch).
 struct vs_conv {
     int kind, c_in, c_out, k, dil, pad;   // dil = stride for transposed
     unsigned flags;

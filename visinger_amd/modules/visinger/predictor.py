@@ -5,7 +5,7 @@ sub-module names -- ``pitch_predictor`` / ``linear`` and ``phoneme_predictor`` /
 
 Both are "relative-attention encoder + 1x1 projection"; the shared plumbing lives in ``_EncoderHead``.  The projections are
 1x1 convs with 2 and ``dict_size`` output rows: the 2-row one takes the engine's small-C_out VALU path
-(csrc/conv_engine.hip, conv_small_kernel), the other one the MFMA path.
+(csrc/conv_small.hip, conv_small_kernel), the other one the MFMA path.
 """
 import torch
 import torch.nn as nn
