@@ -507,6 +507,40 @@ VS_API int vs_guide_deviation(const float *f0_hz, const int64_t *lengths, const 
                               int octave_fold, int32_t *dev_med, int32_t *n_corr, int64_t B, int64_t T, int64_t T_ph, void *stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * f9  sample-rate conversion (csrc/resample.hip): a rational polyphase converter -- recordings at another rate in (f6 tracks them at the
+ *     model's), waveforms at another rate out.  Not in the reference (it resamples on the host through librosa).
+ *     Inputs: integers sr_in, sr_out >= 1, g = gcd(sr_in, sr_out); quality: zeros (integer >= 1, default 32), beta (> 0, default 10.0), rolloff (in (0, 1],
+ *     default 0.90).  L = sr_out / g, M = sr_in / g, S = max(L, M), W = zeros S, fc = rolloff / (2 S).
+ *       Prototype, for integer m with |m| <= W, zero elsewhere:  h(m) = L 2 fc sinc(2 fc m) I0(beta sqrt(1 - (m / W)^2)) / I0(beta),  sinc(x) = sin(pi x) / (pi x);
+ *       evaluated in fp64 ON THE HOST and rounded once to fp32: the device only ever sees the fp32 table, which is part of the input, not of the arithmetic.
+ *       Output: row b has len_b = lengths[b] clamped to [0, n_in] samples and out_len_b = ceil(len_b L / M).  For 0 <= n < min(out_len_b, n_out):
+ *         y[b, n] = sum x[b, i] h(n M - i L) over every i with 0 <= i < len_b and |n M - i L| <= W;   y[b, n] = 0 for the other n < n_out.
+ *       A sample at or beyond len_b is never read into a result.  out_lengths[b] (optional) = out_len_b, not cut at n_out.
+ *     Table (the caller builds it; visinger_amd/resample.py design()): fp32 [L][P], 16-byte aligned, P = 2 C + 1, C = ceil(W / L).  Row rho holds the phase
+ *       p = (rho M) mod L -- the phase of every output n with n mod L = rho, so consecutive outputs read consecutive rows -- and table[rho][j] = h((C - j) L + p).
+ *       With n M = q L + p the output is the sum over j = 0 .. P - 1 of x[q - C + j] table[n mod L][j] (x = 0 outside [0, len_b)).
+ *       Tile: 4 G outputs, G = L max(1, floor((256 + L / 2) / L)) (a whole number of table periods, about 256): vs_resample_tile(L).
+ *       Budget: L P 4 <= VS_RESAMPLE_TABLE_BYTES, and the table plus one tile's input span -- (3 + floor((4 G - 1) M / L) + P + 4) & ~3 floats -- within
+ *       VS_RESAMPLE_LDS_BYTES; M <= VS_RESAMPLE_MAX_M.  vs_resample_fits answers 1 / 0 for (L, M, P).  At the default quality 24000 <-> 48000,
+ *       24000 <-> 44100, 16000 -> 24000, 22050 -> 24000 and 32000 -> 24000 fit (tables of at most 41600 bytes); 44100 -> 8000 does not.
+ *     Device arithmetic: products and sums in fp32.  One output is ONE chain acc = fmaf(x[q - C + j], table[n mod L][j], acc) from acc = 0 over j = 0 .. P - 1
+ *       ascending (ascending i); terms outside [0, len_b) or outside the prototype enter as products with an exact 0 (so a NaN or infinity at distance up to C
+ *       samples reaches an output, not only one within W / L).  The order does not depend on B, the row, the padding, n_in, n_out or the launch shape: two
+ *       calls that give an output the same samples give it the same bits.  All index arithmetic that involves n M is 64-bit.
+ *     One launch: a workgroup loads the table into LDS once and walks tiles of its row, staging each tile's input span with 16-byte loads (when x is
+ *     16-byte aligned and n_in % 4 == 0); a lane takes the four outputs n0 + c + r G of a tile, which share a table row.  Every element of y is written.
+ *     VS_EINVAL before anything is launched: NULL x / table / y, aliased buffers, B, n_in, n_out <= 0 or n_in, n_out >= 2^40, L or M < 1, M > VS_RESAMPLE_MAX_M,
+ *     P even or < 3, a table over its budget, table and span over the LDS budget, a misaligned table.  No allocation, no atomics, no host synchronisation;
+ *     x and lengths are read on the device and out_lengths is written there: a captured graph replays on other samples and lengths by overwriting them.   */
+#define VS_RESAMPLE_TABLE_BYTES 49152
+#define VS_RESAMPLE_LDS_BYTES 65536
+#define VS_RESAMPLE_MAX_M 1048576
+VS_API int64_t vs_resample_tile(int L);
+VS_API int vs_resample_fits(int L, int M, int P);
+VS_API int vs_resample_poly(const float *x, const int64_t *lengths, int64_t B, int64_t n_in, const float *table, int L, int M, int P, float *y,
+                            int64_t n_out, int64_t *out_lengths, void *stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * a13 grouped / strided Conv1d of the scale discriminator (modules/discriminator.py:55-60) and its gradients.
  *     x: [B, c_in, T], w: [c_out, c_in/groups, k], y / gy: [B, c_out, T_out], T_out = (T + 2*pad - k)/stride + 1.
  *     vs_gconv1d_bwd_weight writes one plane per batch item, gw_planes [B][c_out, c_in/groups, k]; gw = their sum.

@@ -7,7 +7,7 @@ import torch
 
 from . import guide_align as guide_align_ops
 from . import guide_correct as guide_correct_ops
-from . import pitch, pitch_track, sampling, timing
+from . import pitch, pitch_track, resample, sampling, timing
 
 
 def bucket_by_length(lengths, max_frames_per_batch, max_items_per_batch=256, keys=None):
@@ -205,33 +205,55 @@ class GraphedStep:
 
 
 def guide_items(items, hop_size, device, max_frames_per_batch=32768, fit=True, **track):
-    """Copies of `items` in which a recording "guide_wav" -- a 1-D float array at the model's sample rate -- is replaced by "f0": its pitch curve, tracked on
-    the device (pitch_track.extract_f0(**track), which needs sample_rate) in length buckets -- zero-padded, the lengths in a device tensor -- read back and fitted
+    """Copies of `items` in which a recording "guide_wav" -- a 1-D float array -- is replaced by "f0": its pitch curve, tracked on the device
+    (pitch_track.extract_f0(**track), which needs sample_rate, the model's) in length buckets -- zero-padded, the lengths in a device tensor -- read back and fitted
     to the item's len(mel2ph): a longer curve is cut there, a shorter one padded with 0 (unvoiced: vs_f0_norm_interp bridges it like any gap).  Items without a
-    recording are passed on as they are.  fit=False: the curve keeps its own len(guide_wav) // hop_size frames, the recording's timeline (align_items
-    takes it from there).  ValueError: no sample_rate, an item with both "f0" and "guide_wav", a recording that is not 1-D or shorter than a hop."""
+    recording are passed on as they are.  fit=False: the curve keeps its own frames, the recording's timeline (align_items takes it from there).
+    The recordings are at track["recording_rate"] Hz (default: sample_rate), an item's own "guide_sr" going before it.  A bucket at another rate than sample_rate
+    is converted on the device first (resample.resample) and tracked from there without a trip to the host: the converted lengths travel as the
+    device tensor the converter wrote.  Such a recording of n samples counts out_length(n) = ceil(n sample_rate / rate) samples: buckets and the curve's own
+    length are out_length(n) // hop_size frames.
+    ValueError: no sample_rate, a rate that is no integer >= 1 or that the converter's table budget does not admit, an item with both "f0" and "guide_wav", a
+    recording that is not 1-D or shorter than a hop (after conversion)."""
     if "sample_rate" not in track:
-        raise ValueError("guide_track must contain sample_rate (the rate of the recordings, which is the model's)")
-    if set(track) - {"sample_rate", "f0_min", "f0_max", "window", "threshold", "silence"}:
-        raise ValueError(f"guide_track takes sample_rate, f0_min, f0_max, window, threshold and silence, got {sorted(track)}")
+        raise ValueError("guide_track must contain sample_rate (the model's rate; recording_rate is the recordings', where it differs)")
+    if set(track) - {"sample_rate", "recording_rate", "f0_min", "f0_max", "window", "threshold", "silence"}:
+        raise ValueError(f"guide_track takes sample_rate, recording_rate, f0_min, f0_max, window, threshold and silence, got {sorted(track)}")
+    track = dict(track)
+    sr = track["sample_rate"]
+    rec_rate = track.pop("recording_rate", None)
     pitch_track.check_args(hop_size, **track)
-    wavs = {}
+    if rec_rate is not None:
+        resample.design(rec_rate, sr)                                 # (ValueError for a rate out of range or a ratio over the table budget)
+    wavs, rates = {}, {}
     for i, it in enumerate(items):
         if it.get("guide_wav") is None:
             continue
         if it.get("f0") is not None:
             raise ValueError(f"item {i} carries both a guide curve ('f0') and a recording ('guide_wav'): give one of them")
+        rates[i] = sr if it.get("guide_sr", rec_rate) is None else it.get("guide_sr", rec_rate)
+        try:
+            resample.design(rates[i], sr)
+        except ValueError as e:
+            raise ValueError(f"item {i}: guide_sr: {e}") from None
         w = np.asarray(it["guide_wav"])
-        if w.ndim != 1 or not np.issubdtype(w.dtype, np.floating) or len(w) < hop_size:
-            raise ValueError(f"item {i}: guide_wav must be a 1-D float array of at least hop_size = {hop_size} samples, got {w.dtype} {w.shape}")
+        if w.ndim != 1 or not np.issubdtype(w.dtype, np.floating) or resample.out_length(len(w), rates[i], sr) < hop_size:
+            raise ValueError(f"item {i}: guide_wav must be a 1-D float array of at least hop_size = {hop_size} samples at {sr} Hz, got {w.dtype} {w.shape}")
         wavs[i] = w.astype(np.float32, copy=False)
     out = [dict(it) for it in items]
-    for idx in _buckets({i: len(w) // hop_size for i, w in wavs.items()}, max_frames_per_batch):
-        wav = _pad_rows([wavs[i] for i in idx], torch.float32)
+    samples = {i: resample.out_length(len(w), rates[i], sr) for i, w in wavs.items()}          # at the model's rate
+    buckets = [idx for r in sorted(set(rates.values()))               # (recordings of one rate share a bucket)
+               for idx in _buckets({i: n // hop_size for i, n in samples.items() if rates[i] == r}, max_frames_per_batch)]
+    for idx in buckets:
+        rate = rates[idx[0]]
+        wav = _pad_rows([wavs[i] for i in idx], torch.float32).to(device)
         lens = torch.tensor([len(wavs[i]) for i in idx], dtype=torch.int64).to(device)
-        f0 = pitch_track.extract_f0(wav.to(device), hop_size, lengths=lens, **track).cpu().numpy()
+        if rate != sr:
+            wav, lens = resample.resample(wav, rate, sr, lengths=lens, return_lengths=True)
+        f0 = pitch_track.extract_f0(wav, hop_size, lengths=lens, **track).cpu().numpy()
         for b, i in enumerate(idx):
-            own = len(wavs[i]) // hop_size
+            out[i].pop("guide_sr", None)
+            own = samples[i] // hop_size
             T, have = (len(items[i]["mel2ph"]), min(own, len(items[i]["mel2ph"]))) if fit else (own, own)
             curve = np.zeros(T, np.float32)
             curve[:have] = f0[b, :have]
@@ -392,7 +414,7 @@ def retime_items(items, tempo, device, max_frames_per_batch=32768):
 @torch.no_grad()
 def synthesize(model, items, hop_size, max_frames_per_batch=32768, noise_scale=1.0, generator=None, equal_tokens=False,
                graphs=None, streams=2, seeds=None, takes=1, first_take=0, voicing="guide", pitch_shift_cents=None, return_f0=False,
-               tempo=None, guide_track=None, guide_align=None, guide_correct=None):
+               tempo=None, guide_track=None, guide_align=None, guide_correct=None, resample_to=None):
     """Run VISinger.forward(infer=True) over length-bucketed batches.  Returns a list of float32 waveforms trimmed to
     each item's own length (frames * hop_size), in the input order.
 
@@ -432,9 +454,10 @@ def synthesize(model, items, hop_size, max_frames_per_batch=32768, noise_scale=1
     copies of the items that carry the retimed alignment, so buckets, `ragged`, graphs and trimming see the new lengths.  The caller's items are not
     modified.  Without tempo and without an item that carries "ph_stretch" there is no pre-pass.
 
-    Guide recordings (guide_items): an item may carry "guide_wav" -- a 1-D float array, a recording at the model's sample rate -- instead of "f0"; its curve is
-    tracked on the device in a pre-pass (pitch_track.extract_f0 with the keywords of guide_track, a dict that must contain sample_rate) and fitted to the item's
-    frames.  The pre-pass runs before the tempo pre-pass, so tempo and "ph_stretch" warp a tracked curve exactly as they warp a given one; the caller's items are
+    Guide recordings (guide_items): an item may carry "guide_wav" -- a 1-D float array, a recording -- instead of "f0"; its curve is tracked on the device in a
+    pre-pass (pitch_track.extract_f0 with the keywords of guide_track, a dict that must contain sample_rate, the model's) and fitted to the item's frames.  A
+    recording at another rate -- guide_track["recording_rate"], or the item's own "guide_sr", which wins -- is converted to the model's on the device first
+    (resample.resample).  The pre-pass runs before the tempo pre-pass, so tempo and "ph_stretch" warp a tracked curve exactly as they warp a given one; the caller's items are
     not modified.  ValueError: an item with "guide_wav" and no guide_track (or one without sample_rate), an item with both "f0" and "guide_wav", a recording that
     is not 1-D or shorter than hop_size.  Without "guide_wav" in any item nothing changes.
 
@@ -448,7 +471,21 @@ def synthesize(model, items, hop_size, max_frames_per_batch=32768, noise_scale=1
     Guide correction (correct_items): guide_correct -- a dict of correct_items keywords, possibly empty -- pulls every guide curve ("f0" given, or tracked)
     of an item with token pitches onto the score: flat notes and drift are taken out, vibrato and scoops stay.  The pre-pass runs after the
     alignment pre-pass -- the curve must have one value per frame of the item's mel2ph, which an aligned item has -- and before the tempo pre-pass, so tempo
-    and "ph_stretch" warp the corrected curve.  The caller's items are not modified.  ValueError: see correct_items.  With guide_correct=None nothing changes."""
+    and "ph_stretch" warp the corrected curve.  The caller's items are not modified.  ValueError: see correct_items.  With guide_correct=None nothing changes.
+
+    Output rate (resample.resample): resample_to -- a dict with sample_rate (the model's) and output_rate, optionally the converter's quality
+    keywords zeros, beta, rolloff -- converts every batch's waveforms on the device, on the batch's own stream, before they are copied to the host: rows
+    B * takes, each frames * hop_size samples long.  Entry i of the result is then out_length(frames_i * hop_size) samples long (per take); a curve asked back
+    with return_f0 stays per frame.  Each waveform equals, bit for bit, resample() of the waveform the call returns without resample_to.  ValueError: not a
+    dict, a missing or unknown key, a value out of range, a ratio over the converter's table budget.  With resample_to=None nothing changes."""
+    rs = None
+    if resample_to is not None:
+        if not isinstance(resample_to, dict) or not {"sample_rate", "output_rate"} <= set(resample_to):
+            raise ValueError(f"resample_to must be a dict with sample_rate and output_rate (and optionally zeros, beta, rolloff) or None, got {resample_to!r:.60}")
+        if set(resample_to) - {"sample_rate", "output_rate"} - set(resample.DEFAULTS):
+            raise ValueError(f"resample_to takes sample_rate, output_rate, {', '.join(resample.DEFAULTS)}, got {sorted(resample_to)}")
+        rs = (resample_to["sample_rate"], resample_to["output_rate"], {k: v for k, v in resample_to.items() if k in resample.DEFAULTS})
+        resample.design(rs[0], rs[1], **rs[2])
     if guide_correct is not None and not isinstance(guide_correct, dict):
         raise ValueError(f"guide_correct must be a dict of correct_items keywords (possibly empty) or None, got {guide_correct!r:.60}")
     if guide_align is not None and not isinstance(guide_align, dict):
@@ -498,10 +535,11 @@ def synthesize(model, items, hop_size, max_frames_per_batch=32768, noise_scale=1
         wav = wav_dev.float().cpu().numpy()             # [B * takes, L], item-major
         f0 = f0_dev.float().cpu().numpy() if return_f0 else None      # [B, T]: the prior ran once per item
         for b, i in enumerate(idx):
+            n = lengths[i] * hop_size if rs is None else resample.out_length(lengths[i] * hop_size, rs[0], rs[1])
             if takes == 1:
-                out[i] = wav[b, :lengths[i] * hop_size].copy()
+                out[i] = wav[b, :n].copy()
             else:
-                out[i] = wav[b * takes:(b + 1) * takes, :lengths[i] * hop_size].copy()
+                out[i] = wav[b * takes:(b + 1) * takes, :n].copy()
             if return_f0:
                 out[i] = (out[i], f0[b, :lengths[i]].copy())
 
@@ -521,19 +559,25 @@ def synthesize(model, items, hop_size, max_frames_per_batch=32768, noise_scale=1
         if "f0_hz" in batch or pitch_shift_cents is not None or return_f0:
             cents_dev = pitch.cents_tensor([pitch_shift_cents[i] for i in idx] if pitch_shift_cents is not None else 0.0, B, device)
             pitch_kw = dict(f0_hz=batch.get("f0_hz"), voicing=voicing, pitch_shift_cents=cents_dev)
+        # output rate: the rows' lengths travel with the batch; the conversion runs behind the step, on the stream the step ran on
+        rows_dev = None if rs is None else torch.tensor([lengths[i] * hop_size for i in idx for _ in range(takes)], dtype=torch.int64).to(device)
+
+        def convert(wav_dev, rows_dev=rows_dev):
+            return wav_dev if rs is None else resample.resample(wav_dev, rs[0], rs[1], lengths=rows_dev, **rs[2])
+
         if graphs is not None:
             key = (B, batch["text_tokens"].shape[1], T, ragged) + key_tail + ("f0_hz" in batch, voicing, cents_dev is not None)
             if key not in graphs or graphs[key].weights != GraphedStep.fingerprint(model):      # (re-captured after a weight update)
                 graphs[key] = GraphedStep(model, batch, noise, ragged, voicing=voicing, cents=cents_dev,
                                           **{k: v for k, v in sample.items() if k != "noise"})
-            wav_dev = graphs[key](batch, noise, seeds=seeds_dev, cents=cents_dev)
+            wav_dev = convert(graphs[key](batch, noise, seeds=seeds_dev, cents=cents_dev))
             collect(idx, wav_dev, None, graphs[key].f0_hz_out)
             continue
 
         def run(batch=batch, sample=sample, ragged=ragged, pitch_kw=pitch_kw):
             ret = model(batch["text_tokens"], batch["pitch_tokens"], batch["dur_tokens"], batch["mel2ph"],
                         spk_id=batch["spk_id"], infer=True, mask_decoder=ragged, **sample, **pitch_kw)
-            return ret["wav_out"], ret.get("f0_hz")
+            return convert(ret["wav_out"]), ret.get("f0_hz")
 
         if rotation is None:
             wav_dev, f0_dev = run()
@@ -542,7 +586,7 @@ def synthesize(model, items, hop_size, max_frames_per_batch=32768, noise_scale=1
         for st in rotation.streams:              # (this batch's inputs were made on the caller's stream)
             st.wait_stream(torch.cuda.current_stream())
         (wav_dev, f0_dev), ev = rotation.run(run)
-        for t in list(batch.values()) + [noise if seeds_dev is None else seeds_dev] + ([] if cents_dev is None else [cents_dev]):
+        for t in list(batch.values()) + [noise if seeds_dev is None else seeds_dev] + ([] if cents_dev is None else [cents_dev]) + ([] if rows_dev is None else [rows_dev]):
             t.record_stream(rotation.streams[(rotation.count - 1) % len(rotation.streams)])      # (their memory is reused only behind that stream's work)
         pending.append((idx, wav_dev, ev, f0_dev))
         if len(pending) > len(rotation.streams):
