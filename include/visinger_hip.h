@@ -541,6 +541,52 @@ VS_API int vs_resample_poly(const float *x, const int64_t *lengths, int64_t B, i
                             int64_t n_out, int64_t *out_lengths, void *stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * f10 guide dynamics (csrc/dynamics.hip): the loudness contour of a recording tracked per frame, compared with the synthesised waveform's own
+ *     and applied to it as a smoothed, limited gain.  Not in the reference (the model has no energy condition).  The conventions are f7's / f8's.
+ *     Level unit: 1/256 of a doubling of POWER (about 0.01176 dB): 256 units double the power, 512 the amplitude.  Host parameters in dB become units on the
+ *     host as rint(dB 256 / (10 log10 2)), in double.  A level curve is fp32 mean-square power per frame; a value that is not finite or <= 0 means "no level
+ *     there" -- the <= 0 convention of vs_retime_frames' curve, which therefore warps a level curve as it is.
+ *     vs_level_track: wav fp32 [B, L];  lengths DEVICE int64 [B], clamped to [0, L], or NULL (= L);  level fp32 [B, T], every element written.
+ *       n_b = min(len_b / hop, T).  Block u is the samples u hop .. u hop + hop - 1.  Block energy E_u, fp32, in a fixed order: partial l (l = 0 .. 63) is the
+ *       chain acc = fmaf(v, v, acc) from 0 over the block's samples j with (j / 4) mod 64 == l, j ascending; then the butterfly e_l += e_{l ^ s}, s = 32, 16,
+ *       .. 1 (the order a wave gets from one 16-byte load per lane and 256 samples; the 4-byte path, taken where the row is not 16-byte aligned or
+ *       hop % 4 != 0, produces the same bits).  Frame level, t < n_b: s = the sum of E_u over u = max(0, t - half) .. min(n_b - 1, t + half), ascending from 0;
+ *       cnt = the number of those blocks;  p = s / (float)(cnt hop), one IEEE division;  p = 0 where s is not finite, and for t >= n_b.  A sample at or
+ *       beyond n_b hop is never read into a result.  A row's output depends on its own samples only: not on B, the row, L, T, the padding or the launch shape.
+ *       One launch: grid (tiles of 64 frames, B); a workgroup computes the E_u of its tile plus `half` blocks on both sides into LDS, then the frame sums.
+ *       VS_EINVAL: NULL wav / level, level overlapping an input, B, L, T <= 0, L or T >= 2^31, hop outside [1, 4096], half outside [0, 8].
+ *     Quantisation (vs_level_offset, vs_level_gain).  A frame has a level when p is finite and > 0; then q = (int) rintf(clamp(256 log2f(p), -2^16, 2^16)) (the
+ *       accurate log2f, one fp32 product).  lengths DEVICE int64 [B] or NULL (= T), clamped to [0, T]: n.  Frame t < n is ACTIVE when the guide and the own
+ *       curve both have a level there and both q >= gate.  d_t = qg_t - qo_t.
+ *     vs_level_offset: guide, own fp32 [B, T];  n_act = the item's number of active frames;  off = floor((2 sum d_t + n_act) / (2 n_act)) over them (int64
+ *       sum), 0 when there are none;  both int32 [B].  One workgroup per item, as in vs_guide_deviation.
+ *     vs_level_gain: offset DEVICE int32 [B] or NULL (0), read clamped to [-2^17, 2^17];  e_t = d_t - offset_b on active frames.  For t < n: S_t = the sum of e_u
+ *       and N_t the count over the active u < n with |u - t| <= window.  Where N_t >= 1: m_t = floor((2 S_t + N_t) / (2 N_t)) and
+ *       k_t = clamp(floor((depth_q m_t + 128) / 256), -down, up);  elsewhere, t >= n included, k_t = 0.  k_out int32 [B, T], every element written.  (A frame
+ *       below the gate -- an unvoiced consonant, a breath -- takes the gain of its neighbours; a row whose guide curve is all 0 gets k = 0 throughout.)
+ *       Ranges: T in [1, 65536] (vs_level_offset too), window in [0, 1024], depth_q in [0, 256], up and down in [0, 4096], gate in [-2^16, 2^16], reserved = 0.
+ *       With these every intermediate fits int32: |q| <= 2^16, |d| <= 2^17, |e| <= 2^18, |S| <= 2049 2^18, |2 S + N| < 2^31, |m| <= 2^18, |depth_q m| <= 2^26.
+ *       One launch: grid (tiles of VS_LEVEL_GAIN_TILE frames, B); the tile plus a halo of `window` frames on both sides is staged in LDS and S, N are
+ *       differences of one workgroup prefix sum, as in vs_guide_correct.  16-byte loads and stores when T % 4 == 0 and guide, own, k_out are 16-byte aligned.
+ *     vs_level_apply: x, y fp32 [B, L];  k int32 [B, T];  lengths in SAMPLES, DEVICE int64 [B], clamped to [0, L], or NULL (= L);  n = min(len_b / hop, T);  y is x
+ *       exactly (in place) or does not overlap it.  For sample i < n hop, in integers (64-bit where i is involved): a = 2 i + 1 - hop;  t0 = floor(a / (2 hop))
+ *       (may be -1);  w = a - 2 hop t0, in [0, 2 hop);  ka = k[clamp(t0, 0, n - 1)], kb = k[clamp(t0 + 1, 0, n - 1)], both read clamped to [-4096, 4096];
+ *       kappa = ka (2 hop - w) + kb w (|kappa| <= 2^25 with hop <= 2048: (float) kappa is exact);  y = x exp2f((float) kappa / (float)(1024 hop)): one fp32
+ *       division, the accurate exp2f, one fp32 product.  The gain is linear in level between frame centres and held before the first and after the last one.
+ *       Where kappa == 0, and for every i >= n hop, y is the bits of x, NaNs included.  One launch, 4 samples a lane: 16-byte loads and stores where
+ *       L % 4 == 0 and x, y are 16-byte aligned.  VS_EINVAL: NULL x / k / y, y overlapping x partly, k or lengths, B, L, T <= 0, L or T >= 2^31, hop outside
+ *       [1, 2048].
+ *     All four: VS_EINVAL before anything is launched, the outputs untouched (also: NULL or overlapping buffers, a parameter out of its range).  No allocation,
+ *     no atomics, no host synchronisation; every per-item input is read on the device: a captured graph replays on other data by overwriting it.        */
+#define VS_LEVEL_GAIN_TILE 1024
+VS_API int vs_level_track(const float *wav, const int64_t *lengths, int64_t B, int64_t L, int hop, int half, float *level, int64_t T, void *stream);
+VS_API int vs_level_offset(const float *guide, const float *own, const int64_t *lengths, int gate, int32_t *off, int32_t *n_act, int64_t B, int64_t T,
+                           void *stream);
+VS_API int vs_level_gain(const float *guide, const float *own, const int64_t *lengths, const int32_t *offset, int gate, int window, int depth_q, int up,
+                         int down, int reserved, int32_t *k_out, int64_t B, int64_t T, void *stream);
+VS_API int vs_level_apply(const float *x, const int32_t *k, const int64_t *lengths, int hop, float *y, int64_t B, int64_t L, int64_t T, void *stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * a13 grouped / strided Conv1d of the scale discriminator (modules/discriminator.py:55-60) and its gradients.
  *     x: [B, c_in, T], w: [c_out, c_in/groups, k], y / gy: [B, c_out, T_out], T_out = (T + 2*pad - k)/stride + 1.
  *     vs_gconv1d_bwd_weight writes one plane per batch item, gw_planes [B][c_out, c_in/groups, k]; gw = their sum.

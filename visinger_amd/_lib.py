@@ -139,6 +139,10 @@ def lib():
     L.vs_resample_tile.restype = i64
     L.vs_resample_fits.argtypes = [ci, ci, ci]
     L.vs_resample_poly.argtypes = [_f32p, vp, i64, i64, _f32p, ci, ci, ci, _f32p, i64, vp, vp]
+    L.vs_level_track.argtypes = [_f32p, vp, i64, i64, ci, ci, _f32p, i64, vp]
+    L.vs_level_offset.argtypes = [_f32p, _f32p, vp, ci, vp, vp, i64, i64, vp]
+    L.vs_level_gain.argtypes = [_f32p, _f32p, vp, vp, ci, ci, ci, ci, ci, ci, vp, i64, i64, vp]
+    L.vs_level_apply.argtypes = [_f32p, vp, vp, ci, _f32p, i64, i64, i64, vp]
     L.vs_expand_states.argtypes = [_f32p, vp, _f32p, i64, i64, i64, i64, ci, ci, vp]
     L.vs_make_positions.argtypes = [_f32p, vp, i64, i64, i64, vp]
     L.vs_slice_segments.argtypes = [_f32p, vp, _f32p, i64, i64, i64, i64, vp]

@@ -5,6 +5,7 @@ int16).  Host-side plumbing only."""
 import numpy as np
 import torch
 
+from . import dynamics
 from . import guide_align as guide_align_ops
 from . import guide_correct as guide_correct_ops
 from . import pitch, pitch_track, resample, sampling, timing
@@ -204,7 +205,7 @@ class GraphedStep:
         return self.out          # the graph's STATIC output buffer: the next replay overwrites it (clone to keep it)
 
 
-def guide_items(items, hop_size, device, max_frames_per_batch=32768, fit=True, **track):
+def guide_items(items, hop_size, device, max_frames_per_batch=32768, fit=True, level=None, **track):
     """Copies of `items` in which a recording "guide_wav" -- a 1-D float array -- is replaced by "f0": its pitch curve, tracked on the device
     (pitch_track.extract_f0(**track), which needs sample_rate, the model's) in length buckets -- zero-padded, the lengths in a device tensor -- read back and fitted
     to the item's len(mel2ph): a longer curve is cut there, a shorter one padded with 0 (unvoiced: vs_f0_norm_interp bridges it like any gap).  Items without a
@@ -213,6 +214,9 @@ def guide_items(items, hop_size, device, max_frames_per_batch=32768, fit=True, *
     is converted on the device first (resample.resample) and tracked from there without a trip to the host: the converted lengths travel as the
     device tensor the converter wrote.  Such a recording of n samples counts out_length(n) = ceil(n sample_rate / rate) samples: buckets and the curve's own
     length are out_length(n) // hop_size frames.
+    level: None, or the half width of dynamics.track_level (an integer in [0, 8]): each bucket's loudness contour is then tracked from the same device tensor
+    the pitch is (after the rate conversion), fitted exactly as the f0 curve is and stored as the item's "level" -- fp32 mean-square power per
+    frame, 0 = no level.  An item that brings its own "level" keeps it.
     ValueError: no sample_rate, a rate that is no integer >= 1 or that the converter's table budget does not admit, an item with both "f0" and "guide_wav", a
     recording that is not 1-D or shorter than a hop (after conversion)."""
     if "sample_rate" not in track:
@@ -223,6 +227,8 @@ def guide_items(items, hop_size, device, max_frames_per_batch=32768, fit=True, *
     sr = track["sample_rate"]
     rec_rate = track.pop("recording_rate", None)
     pitch_track.check_args(hop_size, **track)
+    if level is not None:
+        level = dynamics.check_args(half_width=level)[0]
     if rec_rate is not None:
         resample.design(rec_rate, sr)                                 # (ValueError for a rate out of range or a ratio over the table budget)
     wavs, rates = {}, {}
@@ -251,6 +257,7 @@ def guide_items(items, hop_size, device, max_frames_per_batch=32768, fit=True, *
         if rate != sr:
             wav, lens = resample.resample(wav, rate, sr, lengths=lens, return_lengths=True)
         f0 = pitch_track.extract_f0(wav, hop_size, lengths=lens, **track).cpu().numpy()
+        lvl = None if level is None else dynamics.track_level(wav, hop_size, lengths=lens, half_width=level).cpu().numpy()
         for b, i in enumerate(idx):
             out[i].pop("guide_sr", None)
             own = samples[i] // hop_size
@@ -259,6 +266,9 @@ def guide_items(items, hop_size, device, max_frames_per_batch=32768, fit=True, *
             curve[:have] = f0[b, :have]
             del out[i]["guide_wav"]
             out[i]["f0"] = curve
+            if lvl is not None and out[i].get("level") is None:
+                out[i]["level"] = np.zeros(T, np.float32)
+                out[i]["level"][:have] = lvl[b, :have]
     return out
 
 
@@ -377,8 +387,9 @@ def correct_items(items, device, max_frames_per_batch=32768, **guide_correct):
 
 
 def retime_items(items, tempo, device, max_frames_per_batch=32768):
-    """Copies of `items` with "mel2ph" (and "f0", when present) retimed by the item's "ph_stretch" / its tempo (timing.retime), computed on the device in
-    collated groups and read back; the copies carry no "ph_stretch".  tempo: None, a number, or one number per item, finite and > 0 (ValueError);
+    """Copies of `items` with "mel2ph" (and "f0" and "level", when present) retimed by the item's "ph_stretch" / its tempo (timing.retime), computed on the
+    device in collated groups and read back; the copies carry no "ph_stretch".  A level curve is warped by a second timing.retime(curve=) call, only in
+    groups where an item carries one.  tempo: None, a number, or one number per item, finite and > 0 (ValueError);
     "ph_stretch": one finite factor > 0 per token of the item (ValueError)."""
     n = len(items)
     tempos = [1.0] * n if tempo is None else timing.factor_tensor(tempo, n, "cpu").tolist()
@@ -392,6 +403,8 @@ def retime_items(items, tempo, device, max_frames_per_batch=32768):
             raise ValueError(f"item {i}: a stretch factor must be a finite number > 0")
         if it.get("f0") is not None and np.shape(it["f0"]) != (len(it["mel2ph"]),):
             raise ValueError(f"item {i}: the guide curve has {np.shape(it['f0'])} values for {len(it['mel2ph'])} frames (one value in Hz per frame)")
+        if it.get("level") is not None and np.shape(it["level"]) != (len(it["mel2ph"]),):
+            raise ValueError(f"item {i}: the level curve has {np.shape(it['level'])} values for {len(it['mel2ph'])} frames (one value per frame)")
         stretches.append(st)
     out = [None] * n
     guided = [it.get("f0") is not None for it in items]
@@ -401,6 +414,11 @@ def retime_items(items, tempo, device, max_frames_per_batch=32768):
         curve = _pad_rows([items[i]["f0"] for i in idx], torch.float32, T) if guided[idx[0]] else None
         new, lens, warped = timing.retime(mel2ph=m2p.to(device), T_ph=st.shape[1], stretch=st.to(device), tempo=[tempos[i] for i in idx],
                                           curve=None if curve is None else curve.to(device))
+        levels = None
+        if any(items[i].get("level") is not None for i in idx):
+            empty = np.zeros(0, np.float32)
+            lv = _pad_rows([empty if items[i].get("level") is None else items[i]["level"] for i in idx], torch.float32, T)
+            levels = timing.retime(mel2ph=m2p.to(device), T_ph=st.shape[1], stretch=st.to(device), tempo=[tempos[i] for i in idx], curve=lv.to(device))[2].cpu().numpy()
         new, lens = new.cpu().numpy(), lens.cpu().tolist()
         warped = None if warped is None else warped.cpu().numpy()
         for b, i in enumerate(idx):
@@ -408,13 +426,15 @@ def retime_items(items, tempo, device, max_frames_per_batch=32768):
             out[i]["mel2ph"] = new[b, :lens[b]].copy()
             if warped is not None:
                 out[i]["f0"] = warped[b, :lens[b]].copy()
+            if items[i].get("level") is not None:
+                out[i]["level"] = levels[b, :lens[b]].copy()
     return out
 
 
 @torch.no_grad()
 def synthesize(model, items, hop_size, max_frames_per_batch=32768, noise_scale=1.0, generator=None, equal_tokens=False,
                graphs=None, streams=2, seeds=None, takes=1, first_take=0, voicing="guide", pitch_shift_cents=None, return_f0=False,
-               tempo=None, guide_track=None, guide_align=None, guide_correct=None, resample_to=None):
+               tempo=None, guide_track=None, guide_align=None, guide_correct=None, resample_to=None, guide_dynamics=None):
     """Run VISinger.forward(infer=True) over length-bucketed batches.  Returns a list of float32 waveforms trimmed to
     each item's own length (frames * hop_size), in the input order.
 
@@ -477,7 +497,18 @@ def synthesize(model, items, hop_size, max_frames_per_batch=32768, noise_scale=1
     keywords zeros, beta, rolloff -- converts every batch's waveforms on the device, on the batch's own stream, before they are copied to the host: rows
     B * takes, each frames * hop_size samples long.  Entry i of the result is then out_length(frames_i * hop_size) samples long (per take); a curve asked back
     with return_f0 stays per frame.  Each waveform equals, bit for bit, resample() of the waveform the call returns without resample_to.  ValueError: not a
-    dict, a missing or unknown key, a value out of range, a ratio over the converter's table budget.  With resample_to=None nothing changes."""
+    dict, a missing or unknown key, a value out of range, a ratio over the converter's table budget.  With resample_to=None nothing changes.
+
+    Guide dynamics (dynamics.match_dynamics): guide_dynamics -- a dict of dynamics.DEFAULTS keys, possibly empty -- makes every item with a
+    level curve sing with that curve's dynamics.  The curve is the item's "level" -- fp32 mean-square power, one value per frame, 0 = no level there -- or is
+    tracked from its "guide_wav" in the guide pre-pass (guide_items(level=half_width), from the device tensor the pitch is tracked from).  The alignment
+    pre-pass leaves it alone (it is on "f0"'s timeline), the tempo pre-pass warps it as it warps "f0"; after the pre-passes it must have len(mel2ph) values.
+    Behind the generator, on the batch's own stream (behind a graph's replay, outside the capture) and before resample_to's conversion, the batch's waveforms
+    are measured the same way and scaled per sample by the smoothed, limited gain; rows of items without a level come back bit for bit.  Each waveform equals,
+    bit for bit, match_dynamics() of the waveform the call returns without guide_dynamics.  mode "contour" (the default) applies the guide's shape at the
+    synthesiser's own mean level, "absolute" the guide's level itself.  There is no peak guard or limiter behind a boost: max_boost_db is the only protection.
+    ValueError: not a dict, an unknown key, a value out of range, hop_size over 2048, a level curve of another length than the item's frames, an item with
+    "level" in a call without guide_dynamics.  With guide_dynamics=None and no "level" in any item nothing changes and nothing is launched."""
     rs = None
     if resample_to is not None:
         if not isinstance(resample_to, dict) or not {"sample_rate", "output_rate"} <= set(resample_to):
@@ -486,6 +517,18 @@ def synthesize(model, items, hop_size, max_frames_per_batch=32768, noise_scale=1
             raise ValueError(f"resample_to takes sample_rate, output_rate, {', '.join(resample.DEFAULTS)}, got {sorted(resample_to)}")
         rs = (resample_to["sample_rate"], resample_to["output_rate"], {k: v for k, v in resample_to.items() if k in resample.DEFAULTS})
         resample.design(rs[0], rs[1], **rs[2])
+    dyn = None
+    if guide_dynamics is not None:
+        if not isinstance(guide_dynamics, dict):
+            raise ValueError(f"guide_dynamics must be a dict of dynamics.DEFAULTS keys (possibly empty) or None, got {guide_dynamics!r:.60}")
+        if set(guide_dynamics) - set(dynamics.DEFAULTS):
+            raise ValueError(f"guide_dynamics takes {', '.join(dynamics.DEFAULTS)}, got {sorted(guide_dynamics)}")
+        dyn = dict(guide_dynamics)
+        half_width = dynamics.check_args(**dyn)[0]
+        if not (isinstance(hop_size, int) and 1 <= hop_size <= dynamics.HOP_LIMIT):
+            raise ValueError(f"guide_dynamics needs a hop_size in [1, {dynamics.HOP_LIMIT}], got {hop_size!r}")
+    elif any(it.get("level") is not None for it in items):
+        raise ValueError("an item carries 'level': give guide_dynamics, a dict of dynamics.DEFAULTS keys (possibly empty)")
     if guide_correct is not None and not isinstance(guide_correct, dict):
         raise ValueError(f"guide_correct must be a dict of correct_items keywords (possibly empty) or None, got {guide_correct!r:.60}")
     if guide_align is not None and not isinstance(guide_align, dict):
@@ -494,7 +537,9 @@ def synthesize(model, items, hop_size, max_frames_per_batch=32768, noise_scale=1
     if any(it.get("guide_wav") is not None for it in items):
         if guide_track is None or "sample_rate" not in guide_track:
             raise ValueError("an item carries 'guide_wav': give guide_track, a dict of pitch_track.extract_f0 keywords with sample_rate")
-        items = guide_items(items, hop_size, device, max_frames_per_batch, fit=guide_align is None, **guide_track)
+        if "level" in guide_track:
+            raise ValueError("guide_track has no key 'level': the level curve is tracked when guide_dynamics is given")
+        items = guide_items(items, hop_size, device, max_frames_per_batch, fit=guide_align is None, level=None if dyn is None else half_width, **guide_track)
     if guide_align is not None:
         items = align_items(items, device, max_frames_per_batch, **guide_align)
     if guide_correct is not None:
@@ -523,6 +568,12 @@ def synthesize(model, items, hop_size, max_frames_per_batch=32768, noise_scale=1
     for i, it in enumerate(items):
         if guided[i] and np.shape(it["f0"]) != (len(it["mel2ph"]),):
             raise ValueError(f"item {i}: the guide curve has {np.shape(it['f0'])} values for {len(it['mel2ph'])} frames (one value in Hz per frame)")
+    levels = {}
+    for i, it in enumerate(items):
+        if dyn is not None and it.get("level") is not None:
+            levels[i] = np.asarray(it["level"], dtype=np.float32)
+            if levels[i].shape != (len(it["mel2ph"]),):
+                raise ValueError(f"item {i}: the level curve has {levels[i].shape} values for {len(it['mel2ph'])} frames (one value per frame)")
     keys = [len(it["text_tokens"]) for it in items] if equal_tokens else None
     if any(guided):
         keys = [(g, k) for g, k in zip(guided, keys if keys is not None else [0] * len(items))]
@@ -562,7 +613,15 @@ def synthesize(model, items, hop_size, max_frames_per_batch=32768, noise_scale=1
         # output rate: the rows' lengths travel with the batch; the conversion runs behind the step, on the stream the step ran on
         rows_dev = None if rs is None else torch.tensor([lengths[i] * hop_size for i in idx for _ in range(takes)], dtype=torch.int64).to(device)
 
-        def convert(wav_dev, rows_dev=rows_dev):
+        # guide dynamics: the level rows (zeros for an item without one, repeated per take) travel with the batch; a batch without any launches nothing
+        level_dev = dyn_rows = None
+        if any(i in levels for i in idx):
+            level_dev = _pad_rows([levels.get(i, ()) for i in idx for _ in range(takes)], torch.float32, T).to(device)
+            dyn_rows = rows_dev if rows_dev is not None else torch.tensor([lengths[i] * hop_size for i in idx for _ in range(takes)], dtype=torch.int64).to(device)
+
+        def convert(wav_dev, rows_dev=rows_dev, level_dev=level_dev, dyn_rows=dyn_rows):
+            if level_dev is not None:
+                wav_dev = dynamics.match_dynamics(wav_dev.float(), level_dev, hop_size, lengths=dyn_rows, **dyn)
             return wav_dev if rs is None else resample.resample(wav_dev, rs[0], rs[1], lengths=rows_dev, **rs[2])
 
         if graphs is not None:
@@ -586,7 +645,7 @@ def synthesize(model, items, hop_size, max_frames_per_batch=32768, noise_scale=1
         for st in rotation.streams:              # (this batch's inputs were made on the caller's stream)
             st.wait_stream(torch.cuda.current_stream())
         (wav_dev, f0_dev), ev = rotation.run(run)
-        for t in list(batch.values()) + [noise if seeds_dev is None else seeds_dev] + ([] if cents_dev is None else [cents_dev]) + ([] if rows_dev is None else [rows_dev]):
+        for t in list(batch.values()) + [noise if seeds_dev is None else seeds_dev] + ([] if cents_dev is None else [cents_dev]) + ([] if rows_dev is None else [rows_dev]) + ([] if level_dev is None else [level_dev, dyn_rows]):
             t.record_stream(rotation.streams[(rotation.count - 1) % len(rotation.streams)])      # (their memory is reused only behind that stream's work)
         pending.append((idx, wav_dev, ev, f0_dev))
         if len(pending) > len(rotation.streams):
