@@ -587,6 +587,46 @@ VS_API int vs_level_gain(const float *guide, const float *own, const int64_t *le
 VS_API int vs_level_apply(const float *x, const int32_t *k, const int64_t *lengths, int hop, float *y, int64_t B, int64_t L, int64_t T, void *stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * f11 peak limiter (csrc/limiter.hip): a look-ahead sample-peak limiter for a batch of ragged waveforms -- the ceiling behind f10's boost and
+ *     f9's overshoot.  Not in the reference (it peak-normalises on the host).  The gain is computed in integers and the ceiling is a hard guarantee.
+ *     Unit: f10's, seen from the amplitude: 1/512 of a doubling of AMPLITUDE (= 1/256 of a doubling of power), so a reduction composes with vs_level_apply's gain.
+ *     vs_peak_limit: x, y fp32 [B, L];  lengths DEVICE int64 [B], clamped to [0, L], or NULL (= L): n;  c fp32, the ceiling, finite, 0 < c <= 1 (the host makes
+ *       it from ceiling_db <= 0 as 10^(dB / 20) in double, rounded once to fp32);  window W in [0, VS_PEAK_LIMIT_MAX_WINDOW] samples;  tab DEVICE int32
+ *       [VS_PEAK_LIMIT_TABLE]: tab[j] = ceil(512 log2(1 + (j + 1) / 512)), built on the host in double (the device takes no logarithm): part of the input.
+ *       Per sample i of row b:
+ *       1. Need.  u_i = 0 where i >= n or where |x_i| > c is false (a NaN needs nothing).  Otherwise rho = |x_i| / c, the correctly rounded fp32 quotient
+ *          (>= 1; infinite for an infinite sample or on overflow), e = rho's unbiased exponent (its bits >> 23, less 127), m = its 23 mantissa bits, and
+ *          u_i = min(512 e + tab[m >> 14], VS_PEAK_LIMIT_U_MAX) (12288 units = 24 doublings; what an infinity gets: e = 128).  An upper bound by construction:
+ *          2^(u_i / 512) >= |x_i| / c, at most about 2.3 units (0.027 dB) over the exact need.
+ *       2. Hold.  M_j = the largest u_i over |i - j| <= W, cut at [0, n).
+ *       3. Smooth.  g_i = ceil(S_i / N_i) = (S_i + N_i - 1) / N_i in integers, S_i = the sum of M_j over |j - i| <= W cut at [0, n), N_i the number of its terms;
+ *          g_i = 0 for i >= n.  Every M_j of that sum has i in its own window, so g_i >= u_i: the ramp in front of a peak never lets the peak through.  A lone
+ *          peak gets a triangle of half-width 2 W in the log domain; peaks closer than 2 W + 1 share a plateau.  Everything fits int32: S <= 2049 * 12288.
+ *       4. Apply.  y_i is the bits of x_i where g_i = 0 and everywhere beyond n (a NaN within the row comes back as it is only there: within 2 W of an
+ *          over-ceiling sample it goes through the product and stays a NaN, its payload not promised).  Otherwise y_i = x_i exp2f(-(float) g_i / 512.0f) -- the
+ *          exponent is exact in fp32, the accurate exp2f, one fp32 product -- and then the guard: where |y_i| > c, y_i = copysignf(c, y_i) (exp2f and the product
+ *          round; it also brings an infinity to +-c).  After the call |y_i| <= c holds exactly for every i < n that is not a NaN.
+ *       5. gain int32 [B, L] or NULL: g, every element written when given.  stats int32 [B, 3] or NULL: the number of samples with u_i > 0, the largest g_i,
+ *          the number of samples the guard moved; accumulated with integer vector atomics (order-independent: deterministic); the entry clears it on the
+ *          stream before the launch.
+ *       W = 0 is a per-sample soft clip onto c.  A row with nothing over c comes back bit for bit.  Sample peaks only: inter-sample (true) peaks are not seen.
+ *       A row's result depends on its own samples only: not on B, the row, L, the padding or the launch shape.
+ *       One launch: grid (tiles of VS_PEAK_LIMIT_TILE samples, B), one workgroup per tile; the tile plus 2 W samples on both sides is staged in LDS as u (16-byte
+ *       loads where L % 4 == 0 and x, y, gain are 16-byte aligned, 4-byte loads otherwise: the same bits), the hold is a log-step doubling maximum, the sum a
+ *       difference of one workgroup prefix scan.  A tile that stages no u > 0 copies x's bits.  y == x exactly (in place) is allowed: a tile's halo is then its
+ *       neighbour's output, so ONE workgroup per row walks the tiles in order and carries the left halo's u in LDS (the same bits, B workgroups wide), and tiles
+ *       without a reduction write nothing.
+ *       VS_EINVAL before anything is launched, the outputs untouched: NULL x / y / tab, c not in (0, 1], window outside [0, 1024], B or L < 1, L >= 2^31, y
+ *       overlapping x partly, an output overlapping another buffer.  No allocation, no host synchronisation; x, lengths and tab are read on the device: a
+ *       captured graph replays on other data by overwriting them.                                                                                       */
+#define VS_PEAK_LIMIT_TILE 4096
+#define VS_PEAK_LIMIT_MAX_WINDOW 1024
+#define VS_PEAK_LIMIT_TABLE 512
+#define VS_PEAK_LIMIT_U_MAX 12288
+VS_API int vs_peak_limit(const float *x, const int64_t *lengths, const int32_t *tab, float c, int window, float *y, int32_t *gain, int32_t *stats, int64_t B,
+                         int64_t L, void *stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * a13 grouped / strided Conv1d of the scale discriminator (modules/discriminator.py:55-60) and its gradients.
  *     x: [B, c_in, T], w: [c_out, c_in/groups, k], y / gy: [B, c_out, T_out], T_out = (T + 2*pad - k)/stride + 1.
  *     vs_gconv1d_bwd_weight writes one plane per batch item, gw_planes [B][c_out, c_in/groups, k]; gw = their sum.

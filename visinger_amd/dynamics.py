@@ -167,8 +167,8 @@ def match_dynamics(wav, guide_level, hop_size, lengths=None, return_gain=False, 
     level curve on wav's frames (a row of zeros: that row comes back bit for bit);  lengths: in SAMPLES, see track_level.  The composition: own =
     track_level(wav, frames=T); in mode "contour" (the default) offset = level_offset(guide_level, own), used as a device tensor and never read back -- the
     guide's SHAPE at the synthesiser's own mean level, the right default since the microphone level of a guide is arbitrary -- in mode "absolute" no offset:
-    the guide's level itself;  k = level_gain(..);  apply_gain(wav, k).  params: DEFAULTS' keys.  There is no peak guard behind a boost: max_boost_db is the
-    only protection."""
+    the guide's level itself;  k = level_gain(..);  apply_gain(wav, k).  params: DEFAULTS' keys.  A boost can leave the waveform above full scale:
+    limiter.limit_peaks is the peak guard behind it."""
     if set(params) - set(DEFAULTS):
         raise ValueError(f"match_dynamics takes {', '.join(DEFAULTS)}, got {sorted(params)}")
     half, _, _, _, _, _, contour = check_args(**params)

@@ -8,7 +8,7 @@ import torch
 from . import dynamics
 from . import guide_align as guide_align_ops
 from . import guide_correct as guide_correct_ops
-from . import pitch, pitch_track, resample, sampling, timing
+from . import limiter, pitch, pitch_track, resample, sampling, timing
 
 
 def bucket_by_length(lengths, max_frames_per_batch, max_items_per_batch=256, keys=None):
@@ -434,7 +434,7 @@ def retime_items(items, tempo, device, max_frames_per_batch=32768):
 @torch.no_grad()
 def synthesize(model, items, hop_size, max_frames_per_batch=32768, noise_scale=1.0, generator=None, equal_tokens=False,
                graphs=None, streams=2, seeds=None, takes=1, first_take=0, voicing="guide", pitch_shift_cents=None, return_f0=False,
-               tempo=None, guide_track=None, guide_align=None, guide_correct=None, resample_to=None, guide_dynamics=None):
+               tempo=None, guide_track=None, guide_align=None, guide_correct=None, resample_to=None, guide_dynamics=None, limit=None):
     """Run VISinger.forward(infer=True) over length-bucketed batches.  Returns a list of float32 waveforms trimmed to
     each item's own length (frames * hop_size), in the input order.
 
@@ -506,9 +506,16 @@ def synthesize(model, items, hop_size, max_frames_per_batch=32768, noise_scale=1
     Behind the generator, on the batch's own stream (behind a graph's replay, outside the capture) and before resample_to's conversion, the batch's waveforms
     are measured the same way and scaled per sample by the smoothed, limited gain; rows of items without a level come back bit for bit.  Each waveform equals,
     bit for bit, match_dynamics() of the waveform the call returns without guide_dynamics.  mode "contour" (the default) applies the guide's shape at the
-    synthesiser's own mean level, "absolute" the guide's level itself.  There is no peak guard or limiter behind a boost: max_boost_db is the only protection.
+    synthesiser's own mean level, "absolute" the guide's level itself.  A boost can leave the waveform above full scale: `limit` (below) is the peak guard behind it.
     ValueError: not a dict, an unknown key, a value out of range, hop_size over 2048, a level curve of another length than the item's frames, an item with
-    "level" in a call without guide_dynamics.  With guide_dynamics=None and no "level" in any item nothing changes and nothing is launched."""
+    "level" in a call without guide_dynamics.  With guide_dynamics=None and no "level" in any item nothing changes and nothing is launched.
+
+    Peak limiter (limiter.limit_peaks): limit -- a dict of limiter.DEFAULTS keys, possibly empty: ceiling_db (<= 0, default -1.0) and window
+    (samples on each side, default 128) -- holds every waveform under the ceiling.  It is the last device step, behind guide_dynamics and behind resample_to's
+    conversion (whose Kaiser sinc overshoots), on the batch's own stream (behind a graph's replay, outside the capture): rows B * takes, their lengths at the
+    output rate.  Samples that no reduction reaches -- a whole quiet item -- come back bit for bit.  Each waveform equals, bit for bit, limit_peaks() of the
+    waveform the call returns without limit.  ValueError: not a dict, an unknown key, a value out of range.  With limit=None nothing changes and nothing is
+    launched."""
     rs = None
     if resample_to is not None:
         if not isinstance(resample_to, dict) or not {"sample_rate", "output_rate"} <= set(resample_to):
@@ -529,6 +536,14 @@ def synthesize(model, items, hop_size, max_frames_per_batch=32768, noise_scale=1
             raise ValueError(f"guide_dynamics needs a hop_size in [1, {dynamics.HOP_LIMIT}], got {hop_size!r}")
     elif any(it.get("level") is not None for it in items):
         raise ValueError("an item carries 'level': give guide_dynamics, a dict of dynamics.DEFAULTS keys (possibly empty)")
+    lim = None
+    if limit is not None:
+        if not isinstance(limit, dict):
+            raise ValueError(f"limit must be a dict of limiter.DEFAULTS keys (possibly empty) or None, got {limit!r:.60}")
+        if set(limit) - set(limiter.DEFAULTS):
+            raise ValueError(f"limit takes {', '.join(limiter.DEFAULTS)}, got {sorted(limit)}")
+        lim = dict(limit)
+        limiter.check_args(**lim)
     if guide_correct is not None and not isinstance(guide_correct, dict):
         raise ValueError(f"guide_correct must be a dict of correct_items keywords (possibly empty) or None, got {guide_correct!r:.60}")
     if guide_align is not None and not isinstance(guide_align, dict):
@@ -619,10 +634,18 @@ def synthesize(model, items, hop_size, max_frames_per_batch=32768, noise_scale=1
             level_dev = _pad_rows([levels.get(i, ()) for i in idx for _ in range(takes)], torch.float32, T).to(device)
             dyn_rows = rows_dev if rows_dev is not None else torch.tensor([lengths[i] * hop_size for i in idx for _ in range(takes)], dtype=torch.int64).to(device)
 
-        def convert(wav_dev, rows_dev=rows_dev, level_dev=level_dev, dyn_rows=dyn_rows):
+        # peak limiter: the rows' lengths at the output rate travel with the batch; it runs last, on the stream the step ran on
+        lim_rows = None
+        if lim is not None:
+            lim_rows = torch.tensor([lengths[i] * hop_size if rs is None else resample.out_length(lengths[i] * hop_size, rs[0], rs[1])
+                                     for i in idx for _ in range(takes)], dtype=torch.int64).to(device)
+
+        def convert(wav_dev, rows_dev=rows_dev, level_dev=level_dev, dyn_rows=dyn_rows, lim_rows=lim_rows):
             if level_dev is not None:
                 wav_dev = dynamics.match_dynamics(wav_dev.float(), level_dev, hop_size, lengths=dyn_rows, **dyn)
-            return wav_dev if rs is None else resample.resample(wav_dev, rs[0], rs[1], lengths=rows_dev, **rs[2])
+            if rs is not None:
+                wav_dev = resample.resample(wav_dev, rs[0], rs[1], lengths=rows_dev, **rs[2])
+            return wav_dev if lim_rows is None else limiter.limit_peaks(wav_dev.float().contiguous(), lengths=lim_rows, **lim)
 
         if graphs is not None:
             key = (B, batch["text_tokens"].shape[1], T, ragged) + key_tail + ("f0_hz" in batch, voicing, cents_dev is not None)
@@ -645,7 +668,7 @@ def synthesize(model, items, hop_size, max_frames_per_batch=32768, noise_scale=1
         for st in rotation.streams:              # (this batch's inputs were made on the caller's stream)
             st.wait_stream(torch.cuda.current_stream())
         (wav_dev, f0_dev), ev = rotation.run(run)
-        for t in list(batch.values()) + [noise if seeds_dev is None else seeds_dev] + ([] if cents_dev is None else [cents_dev]) + ([] if rows_dev is None else [rows_dev]) + ([] if level_dev is None else [level_dev, dyn_rows]):
+        for t in list(batch.values()) + [noise if seeds_dev is None else seeds_dev] + ([] if cents_dev is None else [cents_dev]) + ([] if rows_dev is None else [rows_dev]) + ([] if level_dev is None else [level_dev, dyn_rows]) + ([] if lim_rows is None else [lim_rows]):
             t.record_stream(rotation.streams[(rotation.count - 1) % len(rotation.streams)])      # (their memory is reused only behind that stream's work)
         pending.append((idx, wav_dev, ev, f0_dev))
         if len(pending) > len(rotation.streams):
