@@ -253,6 +253,43 @@ def test_driver_limits_the_output(driver, case):
         assert any(not np.array_equal(w, p) for w, p in zip(out, plain))
 
 
+@pytest.mark.parametrize("takes", [1, 2])
+@pytest.mark.parametrize("route", ["one_stream", "streams", "graphs"])
+def test_driver_runs_all_three_stages_on_every_route(driver, route, takes):
+    """guide_dynamics, resample_to and limit in one call, with the curve asked back: each waveform equals, bit for bit, limit_peaks(resample(match_dynamics()))
+    of the waveform the same call on the same route returns without the three -- the item without a level skipping match_dynamics -- and the f0 curve is the
+    plain call's.  This holds the one row-length tensor, the post chain's bundle and the one issue path.  It cannot see a tensor missing from what is recorded
+    on a batch's stream: that is held by construction -- the recorded list is the batch record, into which every device tensor of a batch goes as it is made --
+    and no test tries to provoke the race."""
+    from visinger_amd import dynamics as dy
+    from visinger_amd import resample as rs
+    from visinger_amd import synth
+    m, items, hop, nph = driver
+    frames = [len(it["mel2ph"]) for it in items]
+    route_kw = dict(one_stream=dict(streams=1), streams=dict(streams=2, max_frames_per_batch=40 * nph), graphs=dict(graphs={}))[route]
+    kw = dict(route_kw, seeds=11, takes=takes, return_f0=True)
+    dyn, to = dict(mode="absolute", max_boost_db=12.0, gate_db=-150.0), dict(sample_rate=24000, output_rate=44100)
+    levelled = [dict(it, level=np.full(len(it["mel2ph"]), 1e6, np.float32)) for it in items[:2]] + [items[2]]      # item 2 carries none
+    plain = synth.synthesize(m, items, hop, **dict(kw, **(dict(graphs={}) if route == "graphs" else {})))
+    before = []                                                                  # the first two stages by hand, on the device
+    for (w, _), it in zip(plain, levelled):
+        w = cu(np.atleast_2d(w))
+        if "level" in it:
+            w = dy.match_dynamics(w, cu(np.repeat(it["level"][None], len(w), axis=0)), hop, **dyn)
+        before.append(rs.resample(w, 24000, 44100))
+    lim = dict(ceiling_db=peak_db([w.cpu().numpy() for w in before], -6.0), window=16)      # 6 dB under the loudest sample in front of the limiter
+    c = np.float32(lm.check_args(**lim)[0])
+    assert any((w.abs() > float(c)).any() for w in before)
+    want = [lm.limit_peaks(w, **lim).cpu().numpy() for w in before]
+    for again in range(2 if route == "graphs" else 1):                           # (the second call replays the captured steps)
+        out = synth.synthesize(m, levelled, hop, guide_dynamics=dyn, resample_to=to, limit=lim, **kw)
+        for i, (w, f0) in enumerate(out):
+            assert w.dtype == np.float32 and w.shape == ((takes,) if takes > 1 else ()) + (rs.out_length(frames[i] * hop, 24000, 44100),), (route, i, w.shape)
+            assert np.array_equal(bits(np.atleast_2d(w)), bits(want[i])), (route, takes, i)
+            assert (np.abs(w) <= c).all()
+            assert f0.shape == (frames[i],) and np.array_equal(bits(f0), bits(plain[i][1])), (route, takes, i)
+
+
 def test_driver_quiet_items_and_no_key(driver):
     from visinger_amd import synth
     m, items, hop, nph = driver

@@ -1,4 +1,5 @@
-"""Host-argument rules of the control ops (pitch, timing, pitch_track, guide_align, guide_correct), written once.  A per-item value comes
+"""Host-argument rules of the control ops (pitch, timing, pitch_track, guide_align, guide_correct) and of the waveform ops (resample, dynamics, limiter), written
+once: the key check of a keyword dict, the waveform and `out=` checks, the per-device cache of a host table.  A per-item value comes
 as host numbers -- checked here, ValueError, and copied to the device -- or as a GPU tensor, which is checked for kind only (VisingerHipError), used as it
 is and never read back: a captured graph replays on other values by overwriting that tensor."""
 import ctypes
@@ -38,6 +39,50 @@ def gpu_tensor(who, name, t, dtype, shape):
             return t.contiguous()
     want = ", ".join("*" if s is None else str(s) for s in shape)
     raise VisingerHipError(f"{who}: {name} must be a {dtype} tensor [{want}] on the GPU (there is no CPU path), got {t!r:.80}")
+
+
+def keys(name, given, allowed, none_ok=False):
+    """a copy of the dict `given` whose keys are all among `allowed` (any container of names; a dict lists its keys); ValueError for anything that is no
+    dict and for an unknown key.  none_ok: None is passed on"""
+    if type(given) is dict or isinstance(given, dict):                 # (the exact type first, as in is_int)
+        for k in given:
+            if k not in allowed:
+                raise ValueError(f"{name} takes {', '.join(allowed)}, got {sorted(given, key=str)}")
+        return given.copy()
+    if given is None and none_ok:
+        return None
+    raise ValueError(f"{name} must be a dict{' or None' if none_ok else ''} (keys: {', '.join(allowed)}), got {given!r:.60}")
+
+
+def waveform(who, wav):
+    """(wav.contiguous(), B, L) of an fp32 GPU tensor [B, L] with B > 0 and 0 < L < 2^31; VisingerHipError for anything else"""
+    wav = gpu_tensor(who, "wav", wav, torch.float32, (None, None))
+    B, n = wav.shape
+    if B == 0 or n == 0 or n >= 1 << 31:
+        raise VisingerHipError(f"{who}: B > 0 and 0 < L < 2^31 are required, got {(B, n)}")
+    return wav, B, n
+
+
+def out_like(who, wav, out):
+    """the tensor a waveform op writes: a new one for None; wav itself or a contiguous fp32 GPU tensor of wav's shape is passed on; VisingerHipError otherwise"""
+    if out is None:
+        return torch.empty_like(wav)
+    if not (torch.is_tensor(out) and out.is_cuda and out.dtype == torch.float32 and out.shape == wav.shape and out.is_contiguous()):
+        raise VisingerHipError(f"{who}: out must be a contiguous fp32 GPU tensor of wav's shape {tuple(wav.shape)}, got {out!r:.80}")
+    return out
+
+
+_tables = {}
+
+
+def device_table(device, key, make):
+    """the device copy of the host table make() -- a numpy array -- on `device`: one per (device, key), made on first use and kept"""
+    dev = torch.device(device)
+    k = (dev.type, torch.cuda.current_device() if dev.index is None else dev.index, key)
+    t = _tables.get(k)
+    if t is None:
+        t = _tables[k] = torch.from_numpy(make().copy()).to(dev)
+    return t
 
 
 def per_item_f32(what, value, B, device, positive=False):

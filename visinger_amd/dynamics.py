@@ -69,14 +69,6 @@ def _curves(who, guide, own, lengths):
     return guide, own, A.lengths_i64(who, "lengths", lengths, B, T, guide.device), B, T
 
 
-def _samples(who, wav):
-    wav = A.gpu_tensor(who, "wav", wav, torch.float32, (None, None))
-    B, n = wav.shape
-    if B == 0 or n == 0 or n >= 1 << 31:
-        raise L.VisingerHipError(f"{who}: B > 0 and 0 < L < 2^31 are required, got {(B, n)}")
-    return wav, B, n
-
-
 def track_level(wav, hop_size, lengths=None, half_width=1, frames=None):
     """level fp32 [B, T]: the mean-square power of wav -- fp32 GPU [B, L] -- per frame of hop_size samples, over the frame's block and half_width blocks on
     each side (cut at the row's ends).  Row b has lengths[b] // hop_size frames; the rest of it, and a frame whose sum is not finite, comes back 0: no level.
@@ -87,7 +79,7 @@ def track_level(wav, hop_size, lengths=None, half_width=1, frames=None):
     half = check_args(half_width=half_width)[0]
     if frames is not None and not A.is_int(frames, 1, (1 << 31) - 1):
         raise ValueError(f"frames must be an integer in [1, 2^31), got {frames!r}")
-    wav, B, n = _samples("track_level", wav)
+    wav, B, n = A.waveform("track_level", wav)
     lengths = A.lengths_i64("track_level", "lengths", lengths, B, n, wav.device)
     T = n // hop if frames is None else int(frames)
     if T < 1:
@@ -131,9 +123,7 @@ def level_gain(guide, own, lengths=None, offset_units=None, **params):
     limited to [-max_cut_db, max_boost_db]; a frame below the gate takes its neighbours' gain; 0 where no active frame lies within `window`, and beyond the
     row's length.  offset_units: None (0), an integer, B integers, or an int32 GPU tensor [B] (level_offset's `off`: used as it is, never read back).
     params: DEFAULTS' keys (half_width and mode are checked and not used here)."""
-    if set(params) - set(DEFAULTS):
-        raise ValueError(f"level_gain takes {', '.join(DEFAULTS)}, got {sorted(params)}")
-    _, window, depth_q, up, down, gate, _ = check_args(**params)
+    _, window, depth_q, up, down, gate, _ = check_args(**A.keys("level_gain", params, DEFAULTS))
     guide, own, lengths, B, T = _curves("level_gain", guide, own, lengths)
     offset = _offset_tensor(offset_units, B, guide.device)
     lib = L.require_gpu()
@@ -148,16 +138,13 @@ def apply_gain(wav, k, hop_size, lengths=None, out=None):
     rest -- and every sample whose gain is 0 -- comes back bit for bit.  out: None (a new tensor), wav itself (in place) or an fp32 GPU tensor of wav's shape
     that does not overlap it."""
     hop = _check_hop("apply_gain", hop_size, HOP_LIMIT)
-    wav, B, n = _samples("apply_gain", wav)
+    wav, B, n = A.waveform("apply_gain", wav)
     k = A.gpu_tensor("apply_gain", "k", k, torch.int32, (B, None))
     T = k.shape[1]
     if T < 1:
         raise L.VisingerHipError("apply_gain: k must have at least one frame")
     lengths = A.lengths_i64("apply_gain", "lengths", lengths, B, n, wav.device)
-    if out is None:
-        out = torch.empty_like(wav)
-    elif not (torch.is_tensor(out) and out.is_cuda and out.dtype == torch.float32 and out.shape == wav.shape and out.is_contiguous()):
-        raise L.VisingerHipError(f"apply_gain: out must be a contiguous fp32 GPU tensor of wav's shape {tuple(wav.shape)}, got {out!r:.80}")
+    out = A.out_like("apply_gain", wav, out)
     L.check(L.require_gpu().vs_level_apply(L.ptr(wav), A.vp(k), A.vp(lengths), hop, L.ptr(out), B, n, T, L.stream_ptr()))
     return out
 
@@ -169,11 +156,9 @@ def match_dynamics(wav, guide_level, hop_size, lengths=None, return_gain=False, 
     guide's SHAPE at the synthesiser's own mean level, the right default since the microphone level of a guide is arbitrary -- in mode "absolute" no offset:
     the guide's level itself;  k = level_gain(..);  apply_gain(wav, k).  params: DEFAULTS' keys.  A boost can leave the waveform above full scale:
     limiter.limit_peaks is the peak guard behind it."""
-    if set(params) - set(DEFAULTS):
-        raise ValueError(f"match_dynamics takes {', '.join(DEFAULTS)}, got {sorted(params)}")
-    half, _, _, _, _, _, contour = check_args(**params)
+    half, _, _, _, _, _, contour = check_args(**A.keys("match_dynamics", params, DEFAULTS))
     hop = _check_hop("match_dynamics", hop_size, HOP_LIMIT)
-    wav, B, n = _samples("match_dynamics", wav)
+    wav, B, n = A.waveform("match_dynamics", wav)
     guide_level = A.gpu_tensor("match_dynamics", "guide_level", guide_level, torch.float32, (B, None))
     T = guide_level.shape[1]
     if not 1 <= T <= T_LIMIT:

@@ -75,9 +75,7 @@ def correct_guide(f0_hz, mel2ph, note_midi, lengths=None, offset_cents=None, ret
     was sung in.  params: window (frames on each side that the slow part is the mean of, inside the note), strength (how much of the slow part is taken out,
     0 .. 1), vibrato (the factor on the fast part, 0 .. 2), wild_cents (a frame farther than this from its note is left alone), octave_fold: see check_args
     and "f8".  ValueError for host values out of range, VisingerHipError for tensors of the wrong kind; both before any launch."""
-    if set(params) - set(DEFAULTS):
-        raise ValueError(f"correct_guide takes {', '.join(DEFAULTS)}, got {sorted(params)}")
-    window, strength_q, vibrato_q, wild, fold, reserved = check_args(**params)
+    window, strength_q, vibrato_q, wild, fold, reserved = check_args(**A.keys("correct_guide", params, DEFAULTS))
     auto = isinstance(offset_cents, str) and offset_cents == "auto"
     f0_hz, mel2ph, note_midi, lengths, offset_cents, B, T, T_ph = _inputs("correct_guide", f0_hz, mel2ph, note_midi, lengths, None if auto else offset_cents)
     lib = L.require_gpu()

@@ -42,20 +42,10 @@ def _table():
     return tab
 
 
-_device_tables = {}
-
-
 def reduction_table(device=None):
     """tab[j] = ceil(512 log2(1 + (j + 1) / 512)), j = 0 .. 511, in double: the reduction in units that a quotient whose leading 9 mantissa bits are j needs at
     most.  device=None: the read-only int32 numpy array; otherwise its copy on that device, made on first use and kept"""
-    if device is None:
-        return _table()
-    dev = torch.device(device)
-    k = (dev.type, torch.cuda.current_device() if dev.index is None else dev.index)
-    t = _device_tables.get(k)
-    if t is None:
-        t = _device_tables[k] = torch.from_numpy(_table().copy()).to(dev)
-    return t
+    return _table() if device is None else A.device_table(device, "limiter", _table)
 
 
 def limit_peaks(wav, lengths=None, out=None, return_gain=False, return_stats=False, **params):
@@ -67,18 +57,10 @@ def limit_peaks(wav, lengths=None, out=None, return_gain=False, return_stats=Fal
     int32 [B, 3]: the samples over the ceiling, the largest reduction, the samples the last guard moved.  The result is y, or a tuple (y[, g][, stats]).
     params: DEFAULTS' keys -- ceiling_db (<= 0, default -1.0) and window (samples on each side, default 128; 0: a per-sample soft clip).
     ValueError for host values out of range, VisingerHipError for tensors of the wrong kind; both before any launch."""
-    if set(params) - set(DEFAULTS):
-        raise ValueError(f"limit_peaks takes {', '.join(DEFAULTS)}, got {sorted(params)}")
-    c, window = check_args(**params)
-    wav = A.gpu_tensor("limit_peaks", "wav", wav, torch.float32, (None, None))
-    B, n = wav.shape
-    if B == 0 or n == 0 or n >= 1 << 31:
-        raise L.VisingerHipError(f"limit_peaks: B > 0 and 0 < L < 2^31 are required, got {(B, n)}")
+    c, window = check_args(**A.keys("limit_peaks", params, DEFAULTS))
+    wav, B, n = A.waveform("limit_peaks", wav)
     lengths = A.lengths_i64("limit_peaks", "lengths", lengths, B, n, wav.device)
-    if out is None:
-        out = torch.empty_like(wav)
-    elif not (torch.is_tensor(out) and out.is_cuda and out.dtype == torch.float32 and out.shape == wav.shape and out.is_contiguous()):
-        raise L.VisingerHipError(f"limit_peaks: out must be a contiguous fp32 GPU tensor of wav's shape {tuple(wav.shape)}, got {out!r:.80}")
+    out = A.out_like("limit_peaks", wav, out)
     lib = L.require_gpu()
     gain = torch.empty((B, n), device=wav.device, dtype=torch.int32) if return_gain else None
     stats = torch.empty((B, 3), device=wav.device, dtype=torch.int32) if return_stats else None

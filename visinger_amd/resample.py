@@ -80,19 +80,6 @@ def design(sr_in, sr_out, zeros=32, beta=10.0, rolloff=0.90):
     return _design(int(sr_in), int(sr_out), *check_quality(zeros, beta, rolloff))
 
 
-_device_tables = {}
-
-
-def _table_on(device, key):
-    """the table of _design(*key) on `device`: one copy per device, made on first use"""
-    dev = torch.device(device)
-    k = (dev.type, torch.cuda.current_device() if dev.index is None else dev.index) + key
-    t = _device_tables.get(k)
-    if t is None:
-        t = _device_tables[k] = torch.from_numpy(_design(*key)[4].copy()).to(dev)
-    return t
-
-
 def out_length(n, sr_in, sr_out):
     """ceil(n L / M): the samples a row of n samples becomes"""
     Lr, M = ratio(sr_in, sr_out)
@@ -110,9 +97,7 @@ def resample(wav, sr_in, sr_out, lengths=None, out_len=None, return_lengths=Fals
     return_lengths: also the converted lengths, an int64 GPU tensor [B] written by the kernel (not cut at out_len).
     quality: zeros, beta, rolloff (design()).  Equal rates return wav as it is (and, with return_lengths, lengths as a device tensor).
     ValueError for host values out of range, VisingerHipError for tensors of the wrong kind; both before any launch."""
-    if set(quality) - set(DEFAULTS):
-        raise ValueError(f"resample takes the quality keywords {', '.join(DEFAULTS)}, got {sorted(quality)}")
-    Lr, M, _, P, _ = design(sr_in, sr_out, **quality)
+    Lr, M, _, P, _ = design(sr_in, sr_out, **A.keys("resample", quality, DEFAULTS))
     key = (int(sr_in), int(sr_out)) + check_quality(**quality)
     if out_len is not None and not A.is_int(out_len, 1, (1 << 40) - 1):
         raise ValueError(f"out_len must be an integer in [1, 2^40), got {out_len!r}")
@@ -132,8 +117,9 @@ def resample(wav, sr_in, sr_out, lengths=None, out_len=None, return_lengths=Fals
     x = (wav[None] if one_row else wav).float().contiguous()
     n_out = out_length(n, sr_in, sr_out) if out_len is None else int(out_len)
     lib = L.require_gpu()
+    table = A.device_table(x.device, key, lambda: _design(*key)[4])             # (one copy of the host table per device, made on first use)
     y = torch.empty((B, n_out), device=x.device, dtype=torch.float32)
     out_lengths = torch.empty((B,), device=x.device, dtype=torch.int64) if return_lengths else None
-    L.check(lib.vs_resample_poly(L.ptr(x), A.vp(lengths), B, n, L.ptr(_table_on(x.device, key)), Lr, M, P, L.ptr(y), n_out, A.vp(out_lengths), L.stream_ptr()))
+    L.check(lib.vs_resample_poly(L.ptr(x), A.vp(lengths), B, n, L.ptr(table), Lr, M, P, L.ptr(y), n_out, A.vp(out_lengths), L.stream_ptr()))
     y = y[0] if one_row else y
     return (y, out_lengths) if return_lengths else y

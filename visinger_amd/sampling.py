@@ -30,6 +30,16 @@ def check_seeds(seeds):
     return out
 
 
+def item_seeds(seeds, n):
+    """one checked seed for each of n items: a single integer s gives item i the seed (s + i) mod 2^63, a sequence must hold n seeds (ValueError)"""
+    if isinstance(seeds, int) and not isinstance(seeds, bool):
+        seeds = [(s + i) % SEED_LIMIT for s in check_seeds([seeds]) for i in range(n)]
+    seeds = check_seeds(seeds)
+    if len(seeds) != n:
+        raise ValueError(f"{len(seeds)} seeds for {n} items")
+    return seeds
+
+
 def check_takes(takes, first_take):
     takes, first_take = int(takes), int(first_take)
     if takes < 1 or first_take < 0 or first_take + takes > TAKE_LIMIT:

@@ -5,6 +5,7 @@ int16).  Host-side plumbing only."""
 import numpy as np
 import torch
 
+from . import _args as A
 from . import dynamics
 from . import guide_align as guide_align_ops
 from . import guide_correct as guide_correct_ops
@@ -44,6 +45,13 @@ def _pad_rows(rows, dtype, width=None, fill=0):
     return out
 
 
+def _check_curve(i, item, key):
+    """ValueError, naming item i, unless the item's curve item[key] -- "f0" or "level" -- is None (or missing) or holds one value per frame of its mel2ph"""
+    if item.get(key) is not None and np.shape(item[key]) != (len(item["mel2ph"]),):
+        what, unit = ("guide", "one value in Hz per frame") if key == "f0" else ("level", "one value per frame")
+        raise ValueError(f"item {i}: the {what} curve has {np.shape(item[key])} values for {len(item['mel2ph'])} frames ({unit})")
+
+
 def collate(items, device):
     """items: dicts with int64 1-D arrays text_tokens, pitch_tokens, dur_tokens (T_ph) and mel2ph (T_mel); 0-padded.
     An item may carry "f0": a guide curve in Hz, one value per frame of its mel2ph (0 = unvoiced) -> batch["f0_hz"], fp32 [B, T_mel], padded
@@ -58,8 +66,7 @@ def collate(items, device):
     out["spk_id"] = torch.as_tensor([int(it.get("spk_id", 0)) for it in items], dtype=torch.long)
     if guided and guided[0]:
         for b, it in enumerate(items):
-            if np.shape(it["f0"]) != (len(it["mel2ph"]),):
-                raise ValueError(f"item {b}: the guide curve has {np.shape(it['f0'])} values for {len(it['mel2ph'])} frames (one value in Hz per frame)")
+            _check_curve(b, it, "f0")
         out["f0_hz"] = _pad_rows([it["f0"] for it in items], torch.float32, T)
     return {k: v.to(device) for k, v in out.items()}
 
@@ -205,6 +212,48 @@ class GraphedStep:
         return self.out          # the graph's STATIC output buffer: the next replay overwrites it (clone to keep it)
 
 
+def _check_dynamics(o, hop_size):
+    dynamics.check_args(**o)
+    dynamics._check_hop("guide_dynamics", hop_size, dynamics.HOP_LIMIT)
+
+
+def _check_track(o, hop_size):
+    pitch_track.check_args(hop_size, **{k: v for k, v in o.items() if k != "recording_rate"})
+    if o.get("recording_rate") is not None:
+        resample.design(o["recording_rate"], o["sample_rate"])       # (ValueError for a rate out of range or a ratio over the table budget)
+
+
+def _check_guide_op(o, ops, auto):
+    """the check of guide_align / guide_correct: the op's own keywords, and offset_cents a finite number (with `auto`: or 'auto')"""
+    ops.check_args(**{k: v for k, v in o.items() if k in ops.DEFAULTS})
+    offset = o.get("offset_cents", 0.0)
+    if not (auto and isinstance(offset, str) and offset == "auto") and not (isinstance(offset, (int, float)) and abs(offset) < float("inf")):
+        raise ValueError(f"offset_cents must be a finite number{' or auto' if auto else ''}, got {offset!r}")
+
+
+# The option dicts of synthesize, in the order they are checked: name -> (the keys it must have, the keys it may have, the check of its values -- the op's own
+# check_args or design -- called with the dict and hop_size).  guide_items, align_items and correct_items check their keywords through the same rows.
+OPTIONS = dict(
+    resample_to=(("sample_rate", "output_rate"), ("sample_rate", "output_rate", *resample.DEFAULTS),
+                 lambda o, hop_size: resample.design(o["sample_rate"], o["output_rate"], **{k: o[k] for k in o if k in resample.DEFAULTS})),
+    guide_dynamics=((), tuple(dynamics.DEFAULTS), _check_dynamics),
+    limit=((), tuple(limiter.DEFAULTS), lambda o, hop_size: limiter.check_args(**o)),
+    guide_correct=((), ("midi_of_token", "offset_cents", *guide_correct_ops.DEFAULTS), lambda o, hop_size: _check_guide_op(o, guide_correct_ops, True)),
+    guide_align=((), ("midi_of_token", "offset_cents", *guide_align_ops.DEFAULTS), lambda o, hop_size: _check_guide_op(o, guide_align_ops, False)),
+    guide_track=(("sample_rate",), ("sample_rate", "recording_rate", "f0_min", "f0_max", "window", "threshold", "silence"), _check_track))
+
+
+def _option(name, given, hop_size=None):
+    """a checked copy of the option dict `name` (a row of OPTIONS), or None for None; ValueError: no dict, an unknown or missing key, a value its check refuses"""
+    required, allowed, check = OPTIONS[name]
+    opts = A.keys(name, given, allowed, none_ok=True)
+    if opts is not None:
+        if not all(k in opts for k in required):
+            raise ValueError(f"{name} must contain {' and '.join(required)}, got {sorted(opts)}")
+        check(opts, hop_size)
+    return opts
+
+
 def guide_items(items, hop_size, device, max_frames_per_batch=32768, fit=True, level=None, **track):
     """Copies of `items` in which a recording "guide_wav" -- a 1-D float array -- is replaced by "f0": its pitch curve, tracked on the device
     (pitch_track.extract_f0(**track), which needs sample_rate, the model's) in length buckets -- zero-padded, the lengths in a device tensor -- read back and fitted
@@ -217,20 +266,14 @@ def guide_items(items, hop_size, device, max_frames_per_batch=32768, fit=True, l
     level: None, or the half width of dynamics.track_level (an integer in [0, 8]): each bucket's loudness contour is then tracked from the same device tensor
     the pitch is (after the rate conversion), fitted exactly as the f0 curve is and stored as the item's "level" -- fp32 mean-square power per
     frame, 0 = no level.  An item that brings its own "level" keeps it.
-    ValueError: no sample_rate, a rate that is no integer >= 1 or that the converter's table budget does not admit, an item with both "f0" and "guide_wav", a
+    As synthesize's first pre-pass (guide_track: a dict of these keywords), on copies of the items: tempo and "ph_stretch" warp a tracked curve as they warp a given
+    one; fit=False under guide_align, level = guide_dynamics' half_width.  "guide_wav" without guide_track: ValueError; no "guide_wav": guide_track is not looked at.
+    ValueError: no sample_rate, an unknown keyword, a rate that is no integer >= 1 or that the converter's table budget does not admit, an item with both "f0" and "guide_wav", a
     recording that is not 1-D or shorter than a hop (after conversion)."""
-    if "sample_rate" not in track:
-        raise ValueError("guide_track must contain sample_rate (the model's rate; recording_rate is the recordings', where it differs)")
-    if set(track) - {"sample_rate", "recording_rate", "f0_min", "f0_max", "window", "threshold", "silence"}:
-        raise ValueError(f"guide_track takes sample_rate, recording_rate, f0_min, f0_max, window, threshold and silence, got {sorted(track)}")
-    track = dict(track)
-    sr = track["sample_rate"]
-    rec_rate = track.pop("recording_rate", None)
-    pitch_track.check_args(hop_size, **track)
+    track = _option("guide_track", track, hop_size)
+    sr, rec_rate = track["sample_rate"], track.pop("recording_rate", None)
     if level is not None:
         level = dynamics.check_args(half_width=level)[0]
-    if rec_rate is not None:
-        resample.design(rec_rate, sr)                                 # (ValueError for a rate out of range or a ratio over the table budget)
     wavs, rates = {}, {}
     for i, it in enumerate(items):
         if it.get("guide_wav") is None:
@@ -305,16 +348,14 @@ def align_items(items, device, max_frames_per_batch=32768, **guide_align):
     = a rest), or its "pitch_tokens" mapped through guide_align["midi_of_token"] (a sequence indexed by token id).  Items without a curve or without token
     pitches are passed on as they are.  The other keywords are align_guide's: offset_cents (one number for the call; an item's "guide_offset_cents" goes
     before it), octave_fold and the weights.  Computed on the device in buckets of guide length and read back.
+    As synthesize's alignment pre-pass (guide_align: a dict of these keywords, possibly empty; None: nothing changes): a recording's curve keeps its own
+    len(guide_wav) // hop_size frames (guide_items(fit=False)), so the item is sung with the recording's timing and pitch.  It runs behind the guide pre-pass and
+    before the tempo pre-pass, which acts on the aligned item; "dur_tokens" stay the caller's; a "level" curve is left alone (it is on "f0"'s timeline).
     ValueError: an unknown keyword, a curve that is not 1-D or longer than 65536 frames, an item of more than 1024 tokens, "note_midi" of another length than
     the tokens, a pitch token outside midi_of_token, and an item that cannot be aligned (status 1: no token with frames, or fewer guide frames than such
     tokens) -- named by its index."""
-    table = guide_align.pop("midi_of_token", None)
-    offset = guide_align.pop("offset_cents", 0.0)
-    if set(guide_align) - set(guide_align_ops.DEFAULTS):
-        raise ValueError(f"guide_align takes midi_of_token, offset_cents, {', '.join(guide_align_ops.DEFAULTS)}, got {sorted(guide_align)}")
-    guide_align_ops.check_args(**guide_align)
-    if not (isinstance(offset, (int, float)) and abs(offset) < float("inf")):
-        raise ValueError(f"offset_cents must be a finite number, got {offset!r}")
+    guide_align = _option("guide_align", guide_align)
+    table, offset = guide_align.pop("midi_of_token", None), guide_align.pop("offset_cents", 0.0)
     def curve_of(i, it, n_tok):
         f0 = np.asarray(it["f0"], dtype=np.float32)
         if f0.ndim != 1 or not 1 <= len(f0) <= guide_align_ops.TG_LIMIT or not 1 <= n_tok <= guide_align_ops.T_PH_LIMIT:
@@ -349,20 +390,16 @@ def correct_items(items, device, max_frames_per_batch=32768, **guide_correct):
     sequence indexed by token id), as in align_items.  Items without a curve or without token pitches are passed on as they are.  The other keywords are
     correct_guide's: window, strength, vibrato, wild_cents, octave_fold, and offset_cents -- one number for the call, or "auto" (each item in the key it was
     sung in); an item's "guide_offset_cents" goes before it.  Computed on the device in buckets of length and read back.
+    As synthesize's correction pre-pass (guide_correct: a dict of these keywords, possibly empty; None: nothing changes), on curves given or tracked: it runs behind
+    the alignment pre-pass (an aligned item has one value per frame) and before the tempo pre-pass, which warps the corrected curve.  The caller's items are not modified.
     ValueError: an unknown keyword, a value out of range, a curve that is not 1-D with len(mel2ph) values, an item of more than 65536 frames or 1024 tokens,
     "note_midi" of another length than the tokens, a pitch token outside midi_of_token -- named by the item's index."""
-    table = guide_correct.pop("midi_of_token", None)
-    offset = guide_correct.pop("offset_cents", 0.0)
-    if set(guide_correct) - set(guide_correct_ops.DEFAULTS):
-        raise ValueError(f"guide_correct takes midi_of_token, offset_cents, {', '.join(guide_correct_ops.DEFAULTS)}, got {sorted(guide_correct)}")
-    guide_correct_ops.check_args(**guide_correct)
-    auto = isinstance(offset, str) and offset == "auto"
-    if not auto and not (isinstance(offset, (int, float)) and abs(offset) < float("inf")):
-        raise ValueError(f"offset_cents must be a finite number or 'auto', got {offset!r}")
+    guide_correct = _option("guide_correct", guide_correct)
+    table, offset = guide_correct.pop("midi_of_token", None), guide_correct.pop("offset_cents", 0.0)
+    auto = isinstance(offset, str)
     def curve_of(i, it, n_tok):
+        _check_curve(i, it, "f0")
         f0, n_frames = np.asarray(it["f0"], dtype=np.float32), len(it["mel2ph"])
-        if f0.shape != (n_frames,):
-            raise ValueError(f"item {i}: the guide curve has {f0.shape} values for {n_frames} frames (one value in Hz per frame)")
         if not 1 <= n_frames <= guide_correct_ops.T_LIMIT or not 1 <= n_tok <= guide_correct_ops.T_PH_LIMIT:
             raise ValueError(f"item {i}: a guide curve of 1 .. {guide_correct_ops.T_LIMIT} frames and 1 .. {guide_correct_ops.T_PH_LIMIT} tokens can be "
                              f"corrected, got {n_frames} and {n_tok}")
@@ -390,7 +427,9 @@ def retime_items(items, tempo, device, max_frames_per_batch=32768):
     """Copies of `items` with "mel2ph" (and "f0" and "level", when present) retimed by the item's "ph_stretch" / its tempo (timing.retime), computed on the
     device in collated groups and read back; the copies carry no "ph_stretch".  A level curve is warped by a second timing.retime(curve=) call, only in
     groups where an item carries one.  tempo: None, a number, or one number per item, finite and > 0 (ValueError);
-    "ph_stretch": one finite factor > 0 per token of the item (ValueError)."""
+    "ph_stretch": one finite factor > 0 per token of the item (ValueError).
+    As synthesize's tempo pre-pass, the last one (tempo in input order): mel2ph is retimed by ph_stretch[i] / tempo per token, on copies of the items.  Without
+    tempo and without an item that carries "ph_stretch" there is no pre-pass."""
     n = len(items)
     tempos = [1.0] * n if tempo is None else timing.factor_tensor(tempo, n, "cpu").tolist()
     stretches = []
@@ -401,10 +440,8 @@ def retime_items(items, tempo, device, max_frames_per_batch=32768):
             raise ValueError(f"item {i}: ph_stretch has shape {st.shape} for {len(it['text_tokens'])} tokens (one factor per token)")
         if not (np.isfinite(st).all() and (st > 0).all()):
             raise ValueError(f"item {i}: a stretch factor must be a finite number > 0")
-        if it.get("f0") is not None and np.shape(it["f0"]) != (len(it["mel2ph"]),):
-            raise ValueError(f"item {i}: the guide curve has {np.shape(it['f0'])} values for {len(it['mel2ph'])} frames (one value in Hz per frame)")
-        if it.get("level") is not None and np.shape(it["level"]) != (len(it["mel2ph"]),):
-            raise ValueError(f"item {i}: the level curve has {np.shape(it['level'])} values for {len(it['mel2ph'])} frames (one value per frame)")
+        _check_curve(i, it, "f0")
+        _check_curve(i, it, "level")
         stretches.append(st)
     out = [None] * n
     guided = [it.get("f0") is not None for it in items]
@@ -431,6 +468,52 @@ def retime_items(items, tempo, device, max_frames_per_batch=32768):
     return out
 
 
+class PostChain:
+    """The device stages behind the generator, in their order -- guide dynamics, rate conversion, peak limiter -- built once per synthesize call from its checked
+    option dicts.  A stage whose dict is None is not asked for: nothing changes, it makes no tensor and launches nothing.  The stages run on the batch's own
+    stream (behind a graph's replay, outside the capture), before the waveforms are copied to the host: rows B * takes, each frames * hop_size samples long.
+    Each stage's result equals, bit for bit, its wrapper -- match_dynamics(), resample(), limit_peaks(), which say what the keys mean -- applied to the waveform
+    the call returns without that option.  ValueError (synthesize): an option that is not a dict, an unknown key, a value out of range.
+    guide_dynamics -- a dict of dynamics.DEFAULTS keys, possibly empty -- makes every item with a level curve sing with that curve's dynamics.
+    The curve is the item's "level" -- fp32 mean-square power, one value per frame, 0 = no level there -- given or tracked by the guide pre-pass; after the
+    pre-passes it must have len(mel2ph) values.  The batch's waveforms are measured the same way and scaled per sample by the smoothed, limited gain; rows of
+    items without a level come back bit for bit, and a batch in which no item carries one launches nothing.  ValueError also: hop_size over 2048, a level curve
+    of another length than the item's frames, an item with "level" in a call without guide_dynamics.
+    resample_to -- a dict with sample_rate (the model's) and output_rate, optionally the converter's quality keywords -- converts the waveforms:
+    entry i of the result is then out_length(frames_i * hop_size) samples long (per take); a curve asked back with return_f0 stays per frame.  ValueError also:
+    a missing key, a ratio over the converter's table budget.
+    limit -- a dict of limiter.DEFAULTS keys, possibly empty -- holds every waveform under the ceiling: the last step, behind a guide_dynamics
+    boost and resample_to's conversion, which both overshoot, with the rows' lengths at the output rate.  A whole quiet item comes back bit for bit."""
+
+    def __init__(self, resample_to, guide_dynamics, limit, hop_size, takes):
+        self.dyn, self.lim, self.hop, self.takes = guide_dynamics, limit, hop_size, takes
+        self.rates = None if resample_to is None else (resample_to["sample_rate"], resample_to["output_rate"])
+        self.quality = None if resample_to is None else {k: v for k, v in resample_to.items() if k in resample.DEFAULTS}
+
+    def out_samples(self, frames):
+        """the samples an item of `frames` frames comes back with (per take)"""
+        return frames * self.hop if self.rates is None else resample.out_length(frames * self.hop, *self.rates)
+
+    def batch(self, frames, levels, T, device):
+        """The bundle (apply, tensors) of a batch T frames wide, of items of `frames` frames with the level curves `levels` (None: none).  tensors: what it has put on
+        the device, per take -- the level rows, the rows' lengths at the model's rate (dynamics, converter) and at the output rate (limiter); apply(wav_dev) runs the stages"""
+        rows = lambda per_item: torch.tensor([v for v in per_item for _ in range(self.takes)], dtype=torch.int64).to(device)
+        level = samples = samples_out = None
+        if self.dyn is not None and any(lv is not None for lv in levels):
+            level = _pad_rows([() if lv is None else lv for lv in levels for _ in range(self.takes)], torch.float32, T).to(device)
+        if level is not None or self.rates is not None:
+            samples = rows(n * self.hop for n in frames)
+        if self.lim is not None:
+            samples_out = rows(self.out_samples(n) for n in frames)
+        def apply(wav_dev):
+            if level is not None:
+                wav_dev = dynamics.match_dynamics(wav_dev.float(), level, self.hop, lengths=samples, **self.dyn)
+            if self.rates is not None:
+                wav_dev = resample.resample(wav_dev, *self.rates, lengths=samples, **self.quality)
+            return wav_dev if samples_out is None else limiter.limit_peaks(wav_dev.float().contiguous(), lengths=samples_out, **self.lim)
+        return apply, [t for t in (level, samples, samples_out) if t is not None]
+
+
 @torch.no_grad()
 def synthesize(model, items, hop_size, max_frames_per_batch=32768, noise_scale=1.0, generator=None, equal_tokens=False,
                graphs=None, streams=2, seeds=None, takes=1, first_take=0, voicing="guide", pitch_shift_cents=None, return_f0=False,
@@ -455,9 +538,11 @@ def synthesize(model, items, hop_size, max_frames_per_batch=32768, noise_scale=1
     streams: consecutive batches go to alternating HIP streams (StreamRotation: the next batch's transformers run under this batch's generator); a batch's
     waveforms come back to the host when `streams` later batches have been issued.  The result is bit-identical to streams = 1 (same kernels, same inputs: the
     noise of every batch is drawn on the caller's stream, in batch order).  With `graphs` the batches replay on the caller's stream (one stream).
+    Everything a batch puts on the device -- the collated tensors, noise or seeds, cents, the post chain's tensors -- is kept in one list as it is made, and
+    that list is what is recorded on the batch's stream: the caching allocator reuses their memory only behind that stream's work.
 
-    seeds: one integer in [0, 2^63) per item, in input order, or a single integer s (item i gets (s + i) mod 2^63).  The prior sample of item i is then
-    drawn on the device from the item's own counter-based stream (sampling.prior_sample; noise_scale goes to the kernel) instead of the batch-wide
+    seeds: one integer in [0, 2^63) per item, in input order, or a single integer s (item i gets (s + i) mod 2^63: sampling.item_seeds).  The prior sample of
+    item i is then drawn on the device from the item's own counter-based stream (sampling.prior_sample; noise_scale goes to the kernel) instead of the batch-wide
     torch.randn: the waveform depends on (model, item, seed) only -- not on the bucket, the row, the padding or what was synthesised before.
     takes > 1 (seeded path only): `takes` samples per item, take indices first_take .. first_take + takes - 1, from ONE pass of the text encoder, pitch
     predictor and frame prior; entry i of the result is then a float32 array [takes, frames_i * hop_size].  The padded-frame and item budgets count
@@ -469,96 +554,32 @@ def synthesize(model, items, hop_size, max_frames_per_batch=32768, noise_scale=1
     conditioning curve (guide or predicted), read on the device.  return_f0: the result is a list of (wav, f0_hz) with f0_hz the float32 curve the prior was
     conditioned on, in Hz (0 = unvoiced), trimmed to the item's frames.  Items without "f0" in a call without these arguments run exactly as before.
 
-    Tempo control (timing.retime): tempo -- a number, or one per item in input order, > 0 -- and an item's "ph_stretch" -- one factor > 0 per token -- retime
-    the item's mel2ph by ph_stretch[i] / tempo per token, and warp its "f0" with it, on the device in a pre-pass (retime_items); the call then runs on
-    copies of the items that carry the retimed alignment, so buckets, `ragged`, graphs and trimming see the new lengths.  The caller's items are not
-    modified.  Without tempo and without an item that carries "ph_stretch" there is no pre-pass.
-
-    Guide recordings (guide_items): an item may carry "guide_wav" -- a 1-D float array, a recording -- instead of "f0"; its curve is tracked on the device in a
-    pre-pass (pitch_track.extract_f0 with the keywords of guide_track, a dict that must contain sample_rate, the model's) and fitted to the item's frames.  A
-    recording at another rate -- guide_track["recording_rate"], or the item's own "guide_sr", which wins -- is converted to the model's on the device first
-    (resample.resample).  The pre-pass runs before the tempo pre-pass, so tempo and "ph_stretch" warp a tracked curve exactly as they warp a given one; the caller's items are
-    not modified.  ValueError: an item with "guide_wav" and no guide_track (or one without sample_rate), an item with both "f0" and "guide_wav", a recording that
-    is not 1-D or shorter than hop_size.  Without "guide_wav" in any item nothing changes.
-
-    Guide alignment (align_items): guide_align -- a dict of align_items keywords, possibly empty -- times the score to the guide.  A recording's curve then
-    keeps its own len(guide_wav) // hop_size frames (guide_items(fit=False)), and every item with a curve ("f0" given, of any length, or tracked) and token
-    pitches ("note_midi", or "pitch_tokens" through guide_align["midi_of_token"]) gets the alignment the curve's timing implies: it is sung with the
-    recording's timing and the recording's pitch, len(f0) frames long.  The pre-pass runs between the guide and the tempo pre-pass, so tempo and "ph_stretch"
-    act on the aligned item; buckets, `ragged`, graphs and trimming see the new lengths; "dur_tokens" stay the caller's.  ValueError: see align_items.
-    With guide_align=None nothing changes.
-
-    Guide correction (correct_items): guide_correct -- a dict of correct_items keywords, possibly empty -- pulls every guide curve ("f0" given, or tracked)
-    of an item with token pitches onto the score: flat notes and drift are taken out, vibrato and scoops stay.  The pre-pass runs after the
-    alignment pre-pass -- the curve must have one value per frame of the item's mel2ph, which an aligned item has -- and before the tempo pre-pass, so tempo
-    and "ph_stretch" warp the corrected curve.  The caller's items are not modified.  ValueError: see correct_items.  With guide_correct=None nothing changes.
-
-    Output rate (resample.resample): resample_to -- a dict with sample_rate (the model's) and output_rate, optionally the converter's quality
-    keywords zeros, beta, rolloff -- converts every batch's waveforms on the device, on the batch's own stream, before they are copied to the host: rows
-    B * takes, each frames * hop_size samples long.  Entry i of the result is then out_length(frames_i * hop_size) samples long (per take); a curve asked back
-    with return_f0 stays per frame.  Each waveform equals, bit for bit, resample() of the waveform the call returns without resample_to.  ValueError: not a
-    dict, a missing or unknown key, a value out of range, a ratio over the converter's table budget.  With resample_to=None nothing changes.
-
-    Guide dynamics (dynamics.match_dynamics): guide_dynamics -- a dict of dynamics.DEFAULTS keys, possibly empty -- makes every item with a
-    level curve sing with that curve's dynamics.  The curve is the item's "level" -- fp32 mean-square power, one value per frame, 0 = no level there -- or is
-    tracked from its "guide_wav" in the guide pre-pass (guide_items(level=half_width), from the device tensor the pitch is tracked from).  The alignment
-    pre-pass leaves it alone (it is on "f0"'s timeline), the tempo pre-pass warps it as it warps "f0"; after the pre-passes it must have len(mel2ph) values.
-    Behind the generator, on the batch's own stream (behind a graph's replay, outside the capture) and before resample_to's conversion, the batch's waveforms
-    are measured the same way and scaled per sample by the smoothed, limited gain; rows of items without a level come back bit for bit.  Each waveform equals,
-    bit for bit, match_dynamics() of the waveform the call returns without guide_dynamics.  mode "contour" (the default) applies the guide's shape at the
-    synthesiser's own mean level, "absolute" the guide's level itself.  A boost can leave the waveform above full scale: `limit` (below) is the peak guard behind it.
-    ValueError: not a dict, an unknown key, a value out of range, hop_size over 2048, a level curve of another length than the item's frames, an item with
-    "level" in a call without guide_dynamics.  With guide_dynamics=None and no "level" in any item nothing changes and nothing is launched.
-
-    Peak limiter (limiter.limit_peaks): limit -- a dict of limiter.DEFAULTS keys, possibly empty: ceiling_db (<= 0, default -1.0) and window
-    (samples on each side, default 128) -- holds every waveform under the ceiling.  It is the last device step, behind guide_dynamics and behind resample_to's
-    conversion (whose Kaiser sinc overshoots), on the batch's own stream (behind a graph's replay, outside the capture): rows B * takes, their lengths at the
-    output rate.  Samples that no reduction reaches -- a whole quiet item -- come back bit for bit.  Each waveform equals, bit for bit, limit_peaks() of the
-    waveform the call returns without limit.  ValueError: not a dict, an unknown key, a value out of range.  With limit=None nothing changes and nothing is
-    launched."""
-    rs = None
-    if resample_to is not None:
-        if not isinstance(resample_to, dict) or not {"sample_rate", "output_rate"} <= set(resample_to):
-            raise ValueError(f"resample_to must be a dict with sample_rate and output_rate (and optionally zeros, beta, rolloff) or None, got {resample_to!r:.60}")
-        if set(resample_to) - {"sample_rate", "output_rate"} - set(resample.DEFAULTS):
-            raise ValueError(f"resample_to takes sample_rate, output_rate, {', '.join(resample.DEFAULTS)}, got {sorted(resample_to)}")
-        rs = (resample_to["sample_rate"], resample_to["output_rate"], {k: v for k, v in resample_to.items() if k in resample.DEFAULTS})
-        resample.design(rs[0], rs[1], **rs[2])
-    dyn = None
-    if guide_dynamics is not None:
-        if not isinstance(guide_dynamics, dict):
-            raise ValueError(f"guide_dynamics must be a dict of dynamics.DEFAULTS keys (possibly empty) or None, got {guide_dynamics!r:.60}")
-        if set(guide_dynamics) - set(dynamics.DEFAULTS):
-            raise ValueError(f"guide_dynamics takes {', '.join(dynamics.DEFAULTS)}, got {sorted(guide_dynamics)}")
-        dyn = dict(guide_dynamics)
-        half_width = dynamics.check_args(**dyn)[0]
-        if not (isinstance(hop_size, int) and 1 <= hop_size <= dynamics.HOP_LIMIT):
-            raise ValueError(f"guide_dynamics needs a hop_size in [1, {dynamics.HOP_LIMIT}], got {hop_size!r}")
-    elif any(it.get("level") is not None for it in items):
-        raise ValueError("an item carries 'level': give guide_dynamics, a dict of dynamics.DEFAULTS keys (possibly empty)")
-    lim = None
-    if limit is not None:
-        if not isinstance(limit, dict):
-            raise ValueError(f"limit must be a dict of limiter.DEFAULTS keys (possibly empty) or None, got {limit!r:.60}")
-        if set(limit) - set(limiter.DEFAULTS):
-            raise ValueError(f"limit takes {', '.join(limiter.DEFAULTS)}, got {sorted(limit)}")
-        lim = dict(limit)
-        limiter.check_args(**lim)
-    if guide_correct is not None and not isinstance(guide_correct, dict):
-        raise ValueError(f"guide_correct must be a dict of correct_items keywords (possibly empty) or None, got {guide_correct!r:.60}")
-    if guide_align is not None and not isinstance(guide_align, dict):
-        raise ValueError(f"guide_align must be a dict of align_items keywords (possibly empty) or None, got {guide_align!r:.60}")
+    The controls, in the order their stages run: four pre-passes on the device, on copies of the items -- the call runs on what they leave, so buckets, `ragged`,
+    graphs and trimming see the new lengths and curves -- then three stages behind the generator, on the batch's own stream.  Each option is None (nothing changes, nothing is launched) or a dict, checked through OPTIONS before the model is looked at and before any launch
+    (ValueError), in the order resample_to, guide_dynamics, limit, guide_correct, guide_align, guide_track.
+      1. guide_track      the pitch (and level) curve of an item's recording "guide_wav" is tracked     -> guide_items
+      2. guide_align      the score is timed to the guide curve                                          -> align_items
+      3. guide_correct    the guide curve is pulled onto the score                                       -> correct_items
+      4. tempo            and an item's "ph_stretch": the alignment is retimed, the curves warped        -> retime_items
+      5. guide_dynamics   items with a "level" curve are sung with its dynamics                          -> PostChain, dynamics.match_dynamics
+      6. resample_to      the waveforms are converted to output_rate                                     -> PostChain, resample.resample
+      7. limit            the waveforms are held under a ceiling                                         -> PostChain, limiter.limit_peaks"""
+    sung = any(it.get("guide_wav") is not None for it in items)                  # (no recording: guide_track is not looked at)
+    opts = {}
+    for name, given in zip(OPTIONS, (resample_to, guide_dynamics, limit, guide_correct, guide_align, guide_track if sung else None)):
+        opts[name] = _option(name, given, hop_size)
+        if name == "guide_dynamics" and given is None and any(it.get("level") is not None for it in items):
+            raise ValueError("an item carries 'level': give guide_dynamics, a dict of dynamics.DEFAULTS keys (possibly empty)")
+    if sung and guide_track is None:
+        raise ValueError("an item carries 'guide_wav': give guide_track, a dict of pitch_track.extract_f0 keywords with sample_rate")
     device = next(model.parameters()).device
-    if any(it.get("guide_wav") is not None for it in items):
-        if guide_track is None or "sample_rate" not in guide_track:
-            raise ValueError("an item carries 'guide_wav': give guide_track, a dict of pitch_track.extract_f0 keywords with sample_rate")
-        if "level" in guide_track:
-            raise ValueError("guide_track has no key 'level': the level curve is tracked when guide_dynamics is given")
-        items = guide_items(items, hop_size, device, max_frames_per_batch, fit=guide_align is None, level=None if dyn is None else half_width, **guide_track)
+    if sung:
+        level = None if opts["guide_dynamics"] is None else opts["guide_dynamics"].get("half_width", dynamics.DEFAULTS["half_width"])
+        items = guide_items(items, hop_size, device, max_frames_per_batch, fit=guide_align is None, level=level, **opts["guide_track"])
     if guide_align is not None:
-        items = align_items(items, device, max_frames_per_batch, **guide_align)
+        items = align_items(items, device, max_frames_per_batch, **opts["guide_align"])
     if guide_correct is not None:
-        items = correct_items(items, device, max_frames_per_batch, **guide_correct)
+        items = correct_items(items, device, max_frames_per_batch, **opts["guide_correct"])
     if tempo is not None or any(it.get("ph_stretch") is not None for it in items):
         items = retime_items(items, tempo, device, max_frames_per_batch)
     if voicing not in ("guide", "model"):
@@ -568,109 +589,79 @@ def synthesize(model, items, hop_size, max_frames_per_batch=32768, noise_scale=1
     if seeds is not None:
         if generator is not None:
             raise ValueError("seeds and generator are two sources of the same noise: give one of them")
-        if isinstance(seeds, int) and not isinstance(seeds, bool):
-            sampling.check_seeds([seeds])
-            seeds = [(seeds + i) % sampling.SEED_LIMIT for i in range(len(items))]
-        seeds = sampling.check_seeds(seeds)
-        if len(seeds) != len(items):
-            raise ValueError(f"{len(seeds)} seeds for {len(items)} items")
+        seeds = sampling.item_seeds(seeds, len(items))
         takes, first_take = sampling.check_takes(takes, first_take)
     elif takes != 1 or first_take != 0:
         raise ValueError("takes / first_take select samples of the seeded streams: give seeds")
+    for key in ("f0", "level"):
+        for i, it in enumerate(items):
+            _check_curve(i, it, key)
     lengths = [int((np.asarray(it["mel2ph"]) > 0).sum()) for it in items]
     out = [None] * len(items)
-    guided = ["f0" in it and it["f0"] is not None for it in items]
-    for i, it in enumerate(items):
-        if guided[i] and np.shape(it["f0"]) != (len(it["mel2ph"]),):
-            raise ValueError(f"item {i}: the guide curve has {np.shape(it['f0'])} values for {len(it['mel2ph'])} frames (one value in Hz per frame)")
-    levels = {}
-    for i, it in enumerate(items):
-        if dyn is not None and it.get("level") is not None:
-            levels[i] = np.asarray(it["level"], dtype=np.float32)
-            if levels[i].shape != (len(it["mel2ph"]),):
-                raise ValueError(f"item {i}: the level curve has {levels[i].shape} values for {len(it['mel2ph'])} frames (one value per frame)")
+    guided = [it.get("f0") is not None for it in items]
     keys = [len(it["text_tokens"]) for it in items] if equal_tokens else None
     if any(guided):
         keys = [(g, k) for g, k in zip(guided, keys if keys is not None else [0] * len(items))]
+    chain = PostChain(opts["resample_to"], opts["guide_dynamics"], opts["limit"], hop_size, takes)
     rotation = StreamRotation(streams) if (graphs is None and streams and streams > 1) else None
-    pending = []                                 # (item indices, device waveforms, event) of the batches in flight
+    pending = []                                 # (item indices, device waveforms, device f0, event) of the batches in flight
 
-    def collect(idx, wav_dev, ev, f0_dev=None):
+    def collect(idx, wav_dev, f0_dev, ev=None):
         if ev is not None:
             ev.synchronize()
         wav = wav_dev.float().cpu().numpy()             # [B * takes, L], item-major
         f0 = f0_dev.float().cpu().numpy() if return_f0 else None      # [B, T]: the prior ran once per item
         for b, i in enumerate(idx):
-            n = lengths[i] * hop_size if rs is None else resample.out_length(lengths[i] * hop_size, rs[0], rs[1])
-            if takes == 1:
-                out[i] = wav[b, :n].copy()
-            else:
-                out[i] = wav[b * takes:(b + 1) * takes, :n].copy()
+            n = chain.out_samples(lengths[i])
+            out[i] = wav[b, :n].copy() if takes == 1 else wav[b * takes:(b + 1) * takes, :n].copy()
             if return_f0:
                 out[i] = (out[i], f0[b, :lengths[i]].copy())
 
     for idx in bucket_by_length(lengths, max(1, max_frames_per_batch // takes), max_items_per_batch=max(1, 256 // takes), keys=keys):
         batch = collate([items[i] for i in idx], device)
+        record = list(batch.values())                # the batch record: every tensor this batch puts on the device, as it is made
         B, T = batch["mel2ph"].shape
         ragged = len({lengths[i] for i in idx}) > 1
+        noise = seeds_dev = None
         if seeds is None:
-            noise, seeds_dev = torch.randn((B, model.hidden_size, T), device=device, generator=generator) * noise_scale, None
+            noise = torch.randn((B, model.hidden_size, T), device=device, generator=generator) * noise_scale
             sample, key_tail = dict(noise=noise), ()
         else:                                        # (the seeds travel with the batch; the kernel reads them on the device)
-            noise, seeds_dev = None, torch.tensor([seeds[i] for i in idx], dtype=torch.int64).to(device)
+            seeds_dev = torch.tensor([seeds[i] for i in idx], dtype=torch.int64).to(device)
             sample = dict(seeds=seeds_dev, takes=takes, first_take=first_take, noise_scale=noise_scale)
             key_tail = ("seeded", takes, first_take, float(noise_scale))      # (launch arguments of the sampling kernel: fixed by a capture)
+        record.append(noise if seeds is None else seeds_dev)
         # pitch control: a guided batch, a shift, or the curve asked back (a zero shift leaves the curve's bits alone and makes the model report it)
         cents_dev, pitch_kw = None, {}
         if "f0_hz" in batch or pitch_shift_cents is not None or return_f0:
             cents_dev = pitch.cents_tensor([pitch_shift_cents[i] for i in idx] if pitch_shift_cents is not None else 0.0, B, device)
+            record.append(cents_dev)
             pitch_kw = dict(f0_hz=batch.get("f0_hz"), voicing=voicing, pitch_shift_cents=cents_dev)
-        # output rate: the rows' lengths travel with the batch; the conversion runs behind the step, on the stream the step ran on
-        rows_dev = None if rs is None else torch.tensor([lengths[i] * hop_size for i in idx for _ in range(takes)], dtype=torch.int64).to(device)
-
-        # guide dynamics: the level rows (zeros for an item without one, repeated per take) travel with the batch; a batch without any launches nothing
-        level_dev = dyn_rows = None
-        if any(i in levels for i in idx):
-            level_dev = _pad_rows([levels.get(i, ()) for i in idx for _ in range(takes)], torch.float32, T).to(device)
-            dyn_rows = rows_dev if rows_dev is not None else torch.tensor([lengths[i] * hop_size for i in idx for _ in range(takes)], dtype=torch.int64).to(device)
-
-        # peak limiter: the rows' lengths at the output rate travel with the batch; it runs last, on the stream the step ran on
-        lim_rows = None
-        if lim is not None:
-            lim_rows = torch.tensor([lengths[i] * hop_size if rs is None else resample.out_length(lengths[i] * hop_size, rs[0], rs[1])
-                                     for i in idx for _ in range(takes)], dtype=torch.int64).to(device)
-
-        def convert(wav_dev, rows_dev=rows_dev, level_dev=level_dev, dyn_rows=dyn_rows, lim_rows=lim_rows):
-            if level_dev is not None:
-                wav_dev = dynamics.match_dynamics(wav_dev.float(), level_dev, hop_size, lengths=dyn_rows, **dyn)
-            if rs is not None:
-                wav_dev = resample.resample(wav_dev, rs[0], rs[1], lengths=rows_dev, **rs[2])
-            return wav_dev if lim_rows is None else limiter.limit_peaks(wav_dev.float().contiguous(), lengths=lim_rows, **lim)
+        post, post_tensors = chain.batch([lengths[i] for i in idx], [items[i].get("level") for i in idx], T, device)
+        record += post_tensors
 
         if graphs is not None:
             key = (B, batch["text_tokens"].shape[1], T, ragged) + key_tail + ("f0_hz" in batch, voicing, cents_dev is not None)
             if key not in graphs or graphs[key].weights != GraphedStep.fingerprint(model):      # (re-captured after a weight update)
                 graphs[key] = GraphedStep(model, batch, noise, ragged, voicing=voicing, cents=cents_dev,
                                           **{k: v for k, v in sample.items() if k != "noise"})
-            wav_dev = convert(graphs[key](batch, noise, seeds=seeds_dev, cents=cents_dev))
-            collect(idx, wav_dev, None, graphs[key].f0_hz_out)
-            continue
 
-        def run(batch=batch, sample=sample, ragged=ragged, pitch_kw=pitch_kw):
+        def run():                                   # (called in this iteration, at once: it sees this batch's variables)
+            if graphs is not None:                   # (the post chain runs behind the replay, outside the capture)
+                return post(graphs[key](batch, noise, seeds=seeds_dev, cents=cents_dev)), graphs[key].f0_hz_out
             ret = model(batch["text_tokens"], batch["pitch_tokens"], batch["dur_tokens"], batch["mel2ph"],
                         spk_id=batch["spk_id"], infer=True, mask_decoder=ragged, **sample, **pitch_kw)
-            return convert(ret["wav_out"]), ret.get("f0_hz")
+            return post(ret["wav_out"]), ret.get("f0_hz")
 
         if rotation is None:
-            wav_dev, f0_dev = run()
-            collect(idx, wav_dev, None, f0_dev)
+            collect(idx, *run())
             continue
         for st in rotation.streams:              # (this batch's inputs were made on the caller's stream)
             st.wait_stream(torch.cuda.current_stream())
         (wav_dev, f0_dev), ev = rotation.run(run)
-        for t in list(batch.values()) + [noise if seeds_dev is None else seeds_dev] + ([] if cents_dev is None else [cents_dev]) + ([] if rows_dev is None else [rows_dev]) + ([] if level_dev is None else [level_dev, dyn_rows]) + ([] if lim_rows is None else [lim_rows]):
+        for t in record:
             t.record_stream(rotation.streams[(rotation.count - 1) % len(rotation.streams)])      # (their memory is reused only behind that stream's work)
-        pending.append((idx, wav_dev, ev, f0_dev))
+        pending.append((idx, wav_dev, f0_dev, ev))
         if len(pending) > len(rotation.streams):
             collect(*pending.pop(0))
     for job in pending:
