@@ -78,6 +78,56 @@ void set_last_kernel(const char *fmt, ...) {
     va_end(ap);
 }
 
+// ---- cross-stream ordering of a handle's packed state: see vs_internal.h (StreamOrder).  Both functions touch the HIP runtime only when a
+// stream meets a handle version for the first time; a launch on a known stream costs the comparison in order_read.
+static bool stream_capturing(hipStream_t s) {
+    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(s, &st) != hipSuccess) {
+        (void)hipGetLastError();
+        return true;                    // (cannot tell: leave the stream alone)
+    }
+    return st != hipStreamCaptureStatusNone;
+}
+
+// stream `waiter` waits for everything issued to stream `tail` so far
+static int wait_for_tail(StreamOrder &o, hipStream_t waiter, hipStream_t tail) {
+    if (!o.ev) VS_CHECK_HIP(hipEventCreateWithFlags(&o.ev, hipEventDisableTiming));
+    VS_CHECK_HIP(hipEventRecord(o.ev, tail));
+    VS_CHECK_HIP(hipStreamWaitEvent(waiter, o.ev, 0));      // (the wait holds the record made above: the event may be recorded again at once)
+    return VS_OK;
+}
+
+int order_read_slow(vs_conv *h, hipStream_t s) {
+    StreamOrder &o = h->order;
+    for (hipStream_t k : o.known)
+        if (k == s) {
+            o.last = s;
+            o.any = true;
+            return VS_OK;
+        }
+    if (o.known.empty()) return VS_OK;          // nothing produced yet (the entry points refuse such a handle themselves)
+    if (stream_capturing(s)) return VS_OK;
+    VS_TRY(wait_for_tail(o, s, o.known[0]));
+    o.known.push_back(s);
+    o.last = s;
+    o.any = true;
+    return VS_OK;
+}
+
+int order_write(vs_conv *h, hipStream_t s) {
+    StreamOrder &o = h->order;
+    if (o.known.size() == 1 && o.known[0] == s) return VS_OK;
+    if (!o.known.empty()) {
+        if (stream_capturing(s)) return VS_OK;
+        for (hipStream_t k : o.known)
+            if (k != s) VS_TRY(wait_for_tail(o, s, k));
+    }
+    o.known.assign(1, s);
+    o.last = s;
+    o.any = true;
+    return VS_OK;
+}
+
 
 template <int MT_W, int NT_W, int WAVES_M, int WAVES_N>
 __global__ void __launch_bounds__(64 * WAVES_M * WAVES_N, 2) conv_mfma_kernel(const ConvParams p) {
@@ -715,6 +765,7 @@ int vs_conv_forward(vs_conv_t *h, const vs_conv_io_t *io, void *stream) {
     ConvParams p;
     VS_TRY(fill_params(h, io, p));
     hipStream_t s = as_stream(stream);
+    VS_TRY(order_read(h, s));
     if (opt(OPT_TRACE)) trace_launch(h, p);
     if (small_conv_applies(h, p)) return launch_small_conv(h, p, s);
     if (t1_conv_applies(h, p)) return launch_t1_conv(h, p, s);

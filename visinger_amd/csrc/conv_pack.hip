@@ -311,6 +311,7 @@ static vs_split_pack split_pack_params(const vs_conv *h, bool maxbits_ready) {
 // Winograd-domain fragments of the fp32 engine, from the fp32 fragment buffer Wp of the current weight version
 int pack_wino_weights(vs_conv *h, hipStream_t s) {
     if (h->wino_packed) return VS_OK;
+    VS_TRY(order_write(h, s));         // (s becomes the producing stream of this version: a launch on another stream waits for the transform)
     const size_t nw = (size_t)h->MT_alloc * h->nchunks * h->wino_groups * 2 * 16 * 64;
     VS_TRY(h->wpw.reserve(nw * sizeof(float)));
     PackParams qw;
@@ -350,6 +351,7 @@ int vs_conv_set_math(vs_conv_t *h, int math, void *stream) {
     h->math = math;
     if (math && h->weights_set) {      // a bound handle: the planes of the new arithmetic from the fp32 fragments it already holds
         hipStream_t s = as_stream(stream);
+        VS_TRY(order_write(h, s));
         VS_TRY(reserve_pack_buffers(h, s));
         VS_TRY(pack_split(split_pack_params(h, false), s));
     }
@@ -362,6 +364,7 @@ int vs_conv_set_weights(vs_conv_t *h, const float *w, const float *g, const floa
     VS_REQUIRE(h && w, "vs_conv_set_weights: NULL handle or weight");
     VS_REQUIRE(!(h->flags & VS_CONV_ADJOINT) || !g, "vs_conv_set_weights: an ADJOINT handle takes the plain forward weight (g must be NULL)");
     hipStream_t s = as_stream(stream);
+    VS_TRY(order_write(h, s));
     const float *scale = nullptr;
     if (g) {
         // weight_norm(dim=0): rows = dim 0 of the weight (c_out for Conv1d, c_in for ConvTranspose1d)
@@ -418,6 +421,7 @@ int vs_conv_set_weights_pair(vs_conv_t *h0, vs_conv_t *h1, const float *w, const
     vs_conv *hs[2] = {h0, h1};
     long long work = 0;
     for (int i = 0; i < 2; ++i) {
+        VS_TRY(order_write(hs[i], s));
         VS_TRY(reserve_pack_buffers(hs[i], s));
         q[i] = pack_params(hs[i], w, nullptr, i == 0 ? bias0 : nullptr);
         work = std::max(work, pack_work(hs[i]));
@@ -530,6 +534,7 @@ extern "C" int vs_conv_set_weights_batch(vs_conv_t *const *handles, const float 
     unsigned nb0 = 0, nb1 = 0;
     for (int j = 0; j < m; ++j) {
         vs_conv *h = handles[idx[j]];
+        VS_TRY(order_write(h, s));
         VS_TRY(reserve_pack_buffers(h, s));
         q[j] = pack_params(h, w[idx[j]], nullptr, bias ? bias[idx[j]] : nullptr);
         b0[j] = nb0;

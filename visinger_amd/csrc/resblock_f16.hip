@@ -561,6 +561,7 @@ int vs_resblock_forward(vs_conv_t *const *convs, int nconv, const vs_conv_io_t *
     p.fast_epi = (io->T % 4 == 0) && (p.y_bs % 4 == 0) && (!p.acc || p.acc_bs % 4 == 0) &&
                  (bf ? al8(p.y) && (!p.acc || al8(p.acc)) : al16(p.y) && (!p.acc || al16(p.acc)));
     hipStream_t s = as_stream(stream);
+    for (int i = 0; i < nconv; ++i) VS_TRY(order_read(convs[i], s));
     if (C == 32) {
         // 512-column tiles halve the halo and the weight-fragment traffic per output; with a small halo (k = 3: 12 columns) the 256-column
         // tile's shorter critical path per workgroup wins (tools/resblock_bench.py: k = 3 1.79 vs 1.90 ms, k = 7 3.47 vs 2.87, k = 11 4.87 vs 4.55)

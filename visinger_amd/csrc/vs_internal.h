@@ -6,6 +6,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <vector>
 
 #include "../../include/visinger_hip.h"
 
@@ -99,6 +100,20 @@ struct DevBuf {
 static inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
 static inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+// Which streams may touch a handle's packed state (wp, biasp, scale, weff, beff, wpw, ws, wsc) without further ordering: the stream whose
+// work produced the current version -- the fold and pack of vs_conv_set_weights*, the re-pack of vs_conv_set_math, the F(2,3) transform made
+// inside the first launch that needs it -- and every stream that has since been made to wait for that work.  Host-side only; the calls on one
+// handle come from one thread at a time, as before.
+struct StreamOrder {
+    std::vector<hipStream_t> known;      // known[0]: the producing stream; the rest: streams ordered behind the producing work (the readers)
+    hipStream_t last = nullptr;              // the member of `known` that passed the check most recently: the steady state is this one comparison
+    bool any = false;                    // `last` is set (the NULL stream is a stream like any other)
+    hipEvent_t ev = nullptr;             // made by the first cross-stream use; recorded and waited for within one call, so it is free again on return
+    ~StreamOrder() {
+        if (ev) (void)hipEventDestroy(ev);
+    }
+};
+
 }  // namespace vs
 
 // The conv handle of the C ABI (vs_conv_t), shared by conv_engine.hip (which owns it), conv_pack.hip (which binds its weights), the
@@ -120,7 +135,21 @@ struct vs_conv {
     vs::DevBuf wsc;                            // split-f16 arithmetic (math == 3): {s_w, 1 / s_w, max |w| bits of even / odd packs} of the packed planes
     int pack_gen = 0;                          // weight versions packed in that arithmetic (selects the max slot)
     vs::DevBuf ldpart;                         // PAIRED coupling forward: per-tile log-det partials (fixed-order reduction, no atomics)
+    vs::StreamOrder order;                     // the streams ordered behind the work that produced the packed state above (order_read / order_write)
 };
+
+namespace vs {
+// conv_engine.hip.  order_read: stream s is about to READ h's packed state -- unless it is known to be ordered behind the producing work it is made to wait
+// for the producing stream's tail, once per (version, stream).  order_write: stream s is about to WRITE it (a new version, or the lazily built F(2,3)
+// fragments) -- it is made to wait for the tail of every stream that may still read or produce the previous one, and becomes the producing stream.
+// A capturing stream is left alone in both (an event recorded outside a capture cannot be waited for inside it; whoever captures orders the warm-up before the
+// capture), and is never recorded as a reader.
+int order_read_slow(vs_conv *h, hipStream_t s);
+int order_write(vs_conv *h, hipStream_t s);
+static inline int order_read(vs_conv *h, hipStream_t s) {
+    return (h->order.any && h->order.last == s) ? VS_OK : order_read_slow(h, s);
+}
+}  // namespace vs
 
 
 // resblock_pair_split.hip: the fused residual pair on the split-bf16 x6 arithmetic (both handles in VS_MATH_SPLIT6)

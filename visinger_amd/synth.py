@@ -97,7 +97,11 @@ class StreamRotation:
     mixes utterances), so batch i + 1 issued on a second stream runs its transformers in the gaps of batch i's generator: measured on one
     MI355X, B = 32 x T_mel = 1024: 72.0 -> 69.3 ms a batch; BASELINE configs[1] (B = 8, T_mel = 512): 9.85 -> 8.31 ms; configs[4]: 56.7 -> 54.2 ms
     (profiles/r06_stream_rotation_ab.txt); a third stream adds nothing.  Every launch of the library goes to torch's current stream and every workspace is
-    allocated through torch's stream-aware allocator, so two steps in flight share only read-only state (parameters, packed weights).  NOT for the flow's
+    allocated through torch's stream-aware allocator, so two steps in flight share the parameters, which are read-only, and the conv handles' packed weights.
+    Those are NOT read-only on a cold model or after a parameter change: a handle folds and packs lazily on whichever stream meets it first, and its host-side key
+    is valid before the pack kernels have run.  The library orders that itself (csrc/vs_internal.h StreamOrder): a launch that reads a handle on
+    a stream other than the one its planes were produced on first waits, once per weight version and stream, for the producing stream; a re-pack first waits for
+    the streams that have read the previous version (tests/test_stream_order_gpu.py).  NOT for the flow's
     FORWARD direction with log-det (its partial sums live in the conv handle: INTEGRATION.md 2) nor for training."""
 
     def __init__(self, n=2, timing=False):
@@ -537,7 +541,9 @@ def synthesize(model, items, hop_size, max_frames_per_batch=32768, noise_scale=1
 
     streams: consecutive batches go to alternating HIP streams (StreamRotation: the next batch's transformers run under this batch's generator); a batch's
     waveforms come back to the host when `streams` later batches have been issued.  The result is bit-identical to streams = 1 (same kernels, same inputs: the
-    noise of every batch is drawn on the caller's stream, in batch order).  With `graphs` the batches replay on the caller's stream (one stream).
+    noise of every batch is drawn on the caller's stream, in batch order) -- on a cold model and right after a parameter change too: a batch that meets, on its
+    stream, a handle the previous batch is still packing on the other waits for that pack (StreamRotation).  With `graphs` the batches replay on the caller's
+    stream (one stream).
     Everything a batch puts on the device -- the collated tensors, noise or seeds, cents, the post chain's tensors -- is kept in one list as it is made, and
     that list is what is recorded on the batch's stream: the caching allocator reuses their memory only behind that stream's work.
 
