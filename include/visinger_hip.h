@@ -627,6 +627,39 @@ VS_API int vs_peak_limit(const float *x, const int64_t *lengths, const int32_t *
                          int64_t L, void *stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * f12 pitch tracking as a path (csrc/pitch_track.hip: vs_f0_candidates, csrc/pitch_path.hip: vs_f0_path): f6 decides every frame on its own,
+ *     so a weak fundamental costs a few frames an octave up and a d' near the threshold makes the voicing flicker.  Here a frame keeps SEVERAL lag candidates and
+ *     a Viterbi path over the phrase chooses among them (the pYIN / "Tony" construction, in integers).  Not in the reference.  vs_f0_yin is unchanged.
+ *     vs_f0_candidates.  wav, lengths, B, L, sr, hop, f0_min, f0_max, window, silence, T as in f6; gate in place of threshold.  Outputs cand_hz, cand_d: fp32
+ *     [B, T, 8], EVERY element written.  Steps 1 - 2 of f6 and the energy e of step 4 run unchanged, in f6's summation order: the d' row of a frame holds the same
+ *     bits as in vs_f0_yin.  A frame t < n_b with e finite and e > silence * W has as candidates the lags tau in [tau_min, tau_max], ascending, with
+ *       (tau == tau_min or d'(tau - 1) > d'(tau))  and  d'(tau) <= d'(tau + 1)  and  d'(tau) < gate;
+ *     the first 7 fill slots 0 .. 6: cand_hz = sr / (tau + off) by f6 step 5 (p = tau), cand_d = d'(tau).  Every other slot holds hz = 0, d = 1: slot 7 (the
+ *     unvoiced state's) always, every slot of a silent or non-finite frame and of a frame t >= n_b.
+ *     VS_EINVAL as in f6, with gate finite and > 0 in place of threshold (and B T 8 in range).  One launch, no allocation, no atomics, no host synchronisation.
+ *     vs_f0_path.  cand_hz, cand_d: fp32 [B, T, 8] (slot 7 is not read);  n_frames: DEVICE int64 [B] or NULL (= T), clamped to [0, T]: N;  outputs f0_hz fp32
+ *     [B, T], state int32 [B, T] or NULL, cost int32 [B] or NULL.  States 0 .. 6 are the candidate slots, state 7 is "unvoiced".  Integer once quantised:
+ *       present(t, k): cand_hz finite and > 0.   q(t, k): f7's frame quantiser of cand_hz (unit: 1/16 semitone), the same code.
+ *       loc(t, k) = min((int) rintf(1024 clamp(cand_d, 0, 1)), 1024) + w_order k for a present slot (a NaN d counts as 1); an absent slot: 16384.
+ *       loc(t, 7) = w_unvoiced.
+ *       trans(i -> j) at frame t: 0 when both are unvoiced;  w_switch when exactly one is;  0 when both are voiced and one of them is absent;
+ *                                 otherwise min((abs(q(t-1, i) - q(t, j)) w_jump) >> 4, jump_cap).
+ *       D(0, s) = loc(0, s);  D(t, j) = loc(t, j) + min_i (D(t-1, i) + trans(i -> j)), the lowest i on a tie (the backpointer).
+ *       The end state is the lowest argmin of D(N-1, .), cost that value; then backtrack.  f0_hz[t] = cand_hz[t, s] when s < 7 and the slot is present, else 0;
+ *       state[t] = s.  Frames t >= N: f0_hz = 0, state = -1.  N = 0: cost = 0.
+ *     Weights w_unvoiced, w_switch, w_order, w_jump, jump_cap in [0, 4096] (defaults 160, 96, 24, 32, 384; gate 0.5), reserved = 0, T in [1, 32768].  The worst
+ *     total is 32768 (1024 + 6 * 4096 + 4096) = 973 078 528 < 2^31: int32 holds every D without saturation.
+ *     One wave per item, one launch, sequential over the frames (as f7 is): lane (j, i) forms D(t-1, i) + trans, three xor steps take the minimum.  Backpointers
+ *     are 8 x 3 bits in one dword a frame, in 4 T bytes of dynamic LDS (up to 128 KiB); no workspace.  An item's outputs depend on its own first N frames only.
+ *     VS_EINVAL before anything is launched, nothing written: NULL cand_hz / cand_d / f0_hz, aliased buffers, B < 1, T outside [1, 32768], a weight outside
+ *     [0, 4096], reserved != 0.  No allocation, no atomics, no host synchronisation: a captured graph replays on other candidates by overwriting them.      */
+#define VS_F0_PATH_MAX_FRAMES 32768
+VS_API int vs_f0_candidates(const float *wav, const int64_t *lengths, int64_t B, int64_t L, int sr, int hop, float f0_min, float f0_max, int window,
+                            float gate, float silence, float *cand_hz, float *cand_d, int64_t T, void *stream);
+VS_API int vs_f0_path(const float *cand_hz, const float *cand_d, const int64_t *n_frames, int64_t B, int64_t T, int w_unvoiced, int w_switch, int w_order,
+                      int w_jump, int jump_cap, int reserved, float *f0_hz, int32_t *state, int32_t *cost, void *stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * a13 grouped / strided Conv1d of the scale discriminator (modules/discriminator.py:55-60) and its gradients.
  *     x: [B, c_in, T], w: [c_out, c_in/groups, k], y / gy: [B, c_out, T_out], T_out = (T + 2*pad - k)/stride + 1.
  *     vs_gconv1d_bwd_weight writes one plane per batch item, gw_planes [B][c_out, c_in/groups, k]; gw = their sum.

@@ -132,7 +132,9 @@ def lib():
     L.vs_retime_tokens.argtypes = [vp, vp, _f32p, _f32p, i64, i64, vp, vp, vp, i64, i64, i64, vp]
     L.vs_retime_frames.argtypes = [vp, vp, vp, _f32p, i64, vp, _f32p, i64, i64, i64, vp]
     L.vs_f0_yin.argtypes = [_f32p, vp, i64, i64, ci, ci, cf, cf, ci, cf, cf, _f32p, _f32p, i64, vp]
-    L.vs_guide_align.argtypes = [_f32p, vp, _f32p, vp, _f32p, ci, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, ctypes.c_size_t, i64, i64, i64, vp]
+    L.vs_f0_candidates.argtypes = [_f32p, vp, i64, i64, ci, ci, cf, cf, ci, cf, cf, _f32p, _f32p, i64, vp]
+    L.vs_f0_path.argtypes = [_f32p, _f32p, vp, i64, i64, ci, ci, ci, ci, ci, ci, _f32p, vp, vp, vp]
+    L.vs_guide_align.argtypes =[_f32p, vp, _f32p, vp, _f32p, ci, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, ctypes.c_size_t, i64, i64, i64, vp]
     L.vs_guide_correct.argtypes = [_f32p, vp, vp, _f32p, _f32p, ci, ci, ci, ci, ci, ci, _f32p, vp, i64, i64, i64, vp]
     L.vs_guide_deviation.argtypes = [_f32p, vp, vp, _f32p, _f32p, ci, ci, vp, vp, i64, i64, i64, vp]
     L.vs_resample_tile.argtypes = [ci]

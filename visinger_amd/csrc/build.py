@@ -22,7 +22,9 @@ NO_SCRATCH = {"conv_split.hip": "conv_split_kernel",
               #  kernel counts its vector-memory operations by hand as well)
               "conv_ktap.hip": "conv_ktap_kernel", "conv_ktap_bf16.hip": "conv_ktap_kernel", "conv_ktap_small.hip": "conv_ktap_kernel", "conv_ktap_pair.hip": "conv_ktap_kernel", "attention_dma.hip": "relattn_dma_kernel",
               # (a dependent chain of G frame steps in a 1024-thread workgroup, 128 registers a lane: a spill would be paid once per frame)
-              "guide_align.hip": "guide_align_kernel"}
+              "guide_align.hip": "guide_align_kernel",
+              # (one wave walks the frames of an item in a dependent chain: a spill would be paid once per frame)
+              "pitch_path.hip": "f0_path_kernel"}
 
 
 def check_no_scratch(src, remarks):

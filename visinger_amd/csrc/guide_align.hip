@@ -11,6 +11,7 @@
 //   runs       flags, three scans and a prefix max: E_i - i = max(0, max_{j <= i}(R_j - j)) inside a run.
 // Everything after the two quantisations is integer: bit-reproducible, and a row's result depends on that row only.  No atomics, no host synchronisation.
 #include "vs_internal.h"
+#include "pitch_quant.h"                                // ga_quant, GA_NONE: the frame quantiser, shared with pitch_path.hip
 
 #include <climits>
 #include <cmath>
@@ -22,7 +23,6 @@ constexpr int GA_MAX_FRAMES = 65536;
 constexpr int GA_CHUNK = 256;                           // frames staged at a time
 constexpr int GA_LDS_WORDS = VS_GUIDE_ALIGN_LDS_WORDS;  // backpointer words kept in LDS (40 KiB of the 64)
 constexpr int GA_INF = (1 << 30) - 1;
-constexpr int GA_NONE = INT_MIN;                        // an unvoiced frame / a rest token
 constexpr long long GA_MAX_DUR = (1ll << 24) - 1;
 constexpr int GA_WEIGHT_MAX = 4096;
 
@@ -92,12 +92,6 @@ __device__ __forceinline__ long long ga_scan_max(long long v, long long (*wave_t
 }
 
 __device__ __forceinline__ long long ga_dur(long long d) { return d < 0 ? 0 : (d > GA_MAX_DUR ? GA_MAX_DUR : d); }
-
-__device__ __forceinline__ int ga_quant(float f) {
-    if (!(f > 0.f && f < INFINITY)) return GA_NONE;                           // (NaN fails the compare)
-    const float x = 192.f * log2f(f / 440.f);
-    return (int)rintf(fminf(fmaxf(x, -40000.f), 40000.f)) + 1104;
-}
 
 // what a column brings to c(t, s): its pitch (0 on a rest, never read there), what an unvoiced frame costs on it, and its span [a, e] in the score
 template <typename Pos>

@@ -30,10 +30,10 @@ constexpr int YIN_SCAN = 17;                   // lags per lane of the prefix su
 struct YinArgs {
     const float *wav;
     const long long *lengths;
-    float *f0, *per;
+    float *f0, *per, *cand_hz, *cand_d;                         // yin: f0, per (or NULL); candidates: cand_hz, cand_d [B, T, 8]
     long long B, L, T;
     int sr, hop, W, tau_min, tau_max, G, F, K, n_img, DP;        // G lag groups of 8; K images (1, 2 or 4 shifts); n_img floats per image; DP floats per d' row
-    float thr, silence_w;                                       // silence_w = silence * W (one fp32 product, on the host)
+    float thr, silence_w;                                       // thr: YIN's threshold, or the candidates' gate; silence_w = silence * W (one fp32 product, on the host)
 };
 
 // the eight difference sums of lags 8g .. 8g + 7 for one frame; img: the frame's image, rel (a multiple of 4) = index of x[base] in it.
@@ -82,6 +82,16 @@ __device__ __forceinline__ void yin_lag8(const float *__restrict__ img, int rel,
     }
 }
 
+// step 5 of f6: the parabola through d'(lag - 1 .. lag + 1) and the frequency of its minimum
+__device__ __forceinline__ float yin_hz(const float *d, int lag, int sr) {
+    const float y0 = d[lag - 1], y1 = d[lag], y2 = d[lag + 1], den = y0 - 2.f * y1 + y2;
+    const float off = den > 0.f ? fminf(fmaxf(0.5f * (y0 - y2) / den, -0.5f), 0.5f) : 0.f;
+    return (float)sr / ((float)lag + off);
+}
+
+// CAND = false: vs_f0_yin (steps 3 - 5 of f6 on the d' row).  CAND = true: vs_f0_candidates (f12: the local minima of the same row below the gate).  Everything up
+// to the energy of step 4 is the same code in the same order: a frame's d' row holds the same bits in both.
+template <bool CAND>
 __global__ void __launch_bounds__(YIN_THREADS) yin_kernel(const YinArgs p) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     float *img0 = lds, *dp = lds + p.K * p.n_img;                                         // K images of n_img floats, then d / d' rows [F][DP]
@@ -95,9 +105,17 @@ __global__ void __launch_bounds__(YIN_THREADS) yin_kernel(const YinArgs p) {
         long long n_b = len / p.hop;
         n_b = n_b < p.T ? n_b : p.T;
         const int nf = (int)(n_b - t0 < 0 ? 0 : (n_b - t0 < p.F ? n_b - t0 : p.F));       // frames of this workgroup inside the row
-        for (long long t = t0 + nf + tid; t < t0 + p.F && t < p.T; t += YIN_THREADS) {   // ... and beyond it
-            p.f0[row * p.T + t] = 0.f;
-            if (p.per) p.per[row * p.T + t] = 0.f;
+        if constexpr (CAND) {                                                             // ... and beyond it: every slot empty
+            const long long te = t0 + p.F < p.T ? t0 + p.F : p.T;
+            for (long long i = (t0 + nf) * 8 + tid; i < te * 8; i += YIN_THREADS) {
+                p.cand_hz[row * p.T * 8 + i] = 0.f;
+                p.cand_d[row * p.T * 8 + i] = 1.f;
+            }
+        } else {
+            for (long long t = t0 + nf + tid; t < t0 + p.F && t < p.T; t += YIN_THREADS) {   // ... and beyond it
+                p.f0[row * p.T + t] = 0.f;
+                if (p.per) p.per[row * p.T + t] = 0.f;
+            }
         }
         if (nf == 0) continue;                                                            // (uniform over the workgroup)
         const long long base0 = t0 * p.hop + p.hop / 2 - p.W / 2, lo = base0 - 4 * p.G;  // x[base0] sits at index 4G of image 0
@@ -160,6 +178,36 @@ __global__ void __launch_bounds__(YIN_THREADS) yin_kernel(const YinArgs p) {
             }
 #pragma unroll
             for (int s = 32; s > 0; s >>= 1) e += __shfl_xor(e, s);
+            if constexpr (CAND) {
+                // the lags tau with d'(tau - 1) > d'(tau) <= d'(tau + 1) (tau_min needs no left neighbour) and d'(tau) < gate, ascending: a ballot per 64 lags,
+                // a candidate's slot = the count so far + the candidates in the lanes below it.  Slots 0 .. 6; the rest, slot 7 included, are empty.
+                float *ch = p.cand_hz + (row * p.T + t) * 8, *cd = p.cand_d + (row * p.T + t) * 8;
+                int count = 0;
+                if (fabsf(e) < INFINITY && e > p.silence_w) {
+                    for (int tau0 = p.tau_min; tau0 <= p.tau_max && count < 7; tau0 += 64) {
+                        const int tau = tau0 + lane;
+                        bool c = false;
+                        float v = 1.f;
+                        if (tau <= p.tau_max) {
+                            v = d[tau];
+                            c = v < p.thr && v <= d[tau + 1] && (tau == p.tau_min || d[tau - 1] > v);
+                        }
+                        const unsigned long long m = __ballot(c);
+                        const int slot = count + __popcll(m & ((1ull << lane) - 1ull));
+                        if (c && slot < 7) {
+                            ch[slot] = yin_hz(d, tau, p.sr);
+                            cd[slot] = v;
+                        }
+                        count += __popcll(m);
+                    }
+                    count = count < 7 ? count : 7;
+                }
+                if (lane >= count && lane < 8) {
+                    ch[lane] = 0.f;
+                    cd[lane] = 1.f;
+                }
+                continue;
+            }
             // g = argmin of d' over [tau_min, tau_max], the lowest tau on a tie
             float best = INFINITY;
             int arg = p.tau_max;
@@ -185,9 +233,7 @@ __global__ void __launch_bounds__(YIN_THREADS) yin_kernel(const YinArgs p) {
                 }
                 if (lag) {
                     while (lag + 1 <= p.tau_max && d[lag + 1] < d[lag]) ++lag;            // ... then down to the bottom of its dip
-                    const float y0 = d[lag - 1], y1 = d[lag], y2 = d[lag + 1], den = y0 - 2.f * y1 + y2;
-                    const float off = den > 0.f ? fminf(fmaxf(0.5f * (y0 - y2) / den, -0.5f), 0.5f) : 0.f;
-                    hz = (float)p.sr / ((float)lag + off);
+                    hz = yin_hz(d, lag, p.sr);
                 }
             }
             if (lane == 0) {
@@ -203,30 +249,23 @@ __global__ void __launch_bounds__(YIN_THREADS) yin_kernel(const YinArgs p) {
 
 using namespace vs;
 
-extern "C" {
-
-int vs_f0_yin(const float *wav, const int64_t *lengths, int64_t B, int64_t L, int sr, int hop, float f0_min, float f0_max, int window, float threshold,
-              float silence, float *f0_hz, float *periodicity, int64_t T, void *stream) {
-    VS_REQUIRE(wav && f0_hz, "vs_f0_yin: wav and f0_hz must not be NULL");
-    VS_REQUIRE(wav != f0_hz && wav != periodicity && f0_hz != periodicity && (const void *)lengths != (const void *)f0_hz &&
-                   (!lengths || (const void *)lengths != (const void *)periodicity),
-               "vs_f0_yin: wav, lengths, f0_hz and periodicity must be distinct buffers");
-    VS_REQUIRE(B > 0 && L > 0 && T > 0, "vs_f0_yin: B, L, T must be positive (got %lld, %lld, %lld)", (long long)B, (long long)L, (long long)T);
-    VS_REQUIRE(L < (1ll << 31) && T < (1ll << 31) && B <= INT64_MAX / T && B <= INT64_MAX / L, "vs_f0_yin: L = %lld or T = %lld is not below 2^31, or B * L / B * T is out of range",
-               (long long)L, (long long)T);
-    VS_REQUIRE(hop >= 1 && sr >= 1, "vs_f0_yin: hop = %d and sr = %d must be at least 1", hop, sr);
+// the checks and the launch shape the two entry points share; `what`: "threshold" or "gate"
+static int yin_setup(const char *who, const char *what, int64_t B, int64_t L, int sr, int hop, float f0_min, float f0_max, int window, float threshold,
+                     float silence, int64_t T, YinArgs &a, size_t &lds_bytes) {
+    VS_REQUIRE(B > 0 && L > 0 && T > 0, "%s: B, L, T must be positive (got %lld, %lld, %lld)", who, (long long)B, (long long)L, (long long)T);
+    VS_REQUIRE(L < (1ll << 31) && T < (1ll << 31) && B <= INT64_MAX / T && B <= INT64_MAX / L, "%s: L = %lld or T = %lld is not below 2^31, or B * L / B * T is out of range",
+               who, (long long)L, (long long)T);
+    VS_REQUIRE(hop >= 1 && sr >= 1, "%s: hop = %d and sr = %d must be at least 1", who, hop, sr);
     VS_REQUIRE(f0_min > 0.f && f0_min < INFINITY && f0_max > 0.f && f0_max < INFINITY && f0_min < f0_max,
-               "vs_f0_yin: 0 < f0_min < f0_max < inf is required (got %g, %g)", (double)f0_min, (double)f0_max);
-    VS_REQUIRE(threshold > 0.f && threshold < INFINITY, "vs_f0_yin: threshold = %g is not a finite number > 0", (double)threshold);
-    VS_REQUIRE(silence >= 0.f, "vs_f0_yin: silence = %g is negative (or NaN)", (double)silence);
+               "%s: 0 < f0_min < f0_max < inf is required (got %g, %g)", who, (double)f0_min, (double)f0_max);
+    VS_REQUIRE(threshold > 0.f && threshold < INFINITY, "%s: %s = %g is not a finite number > 0", who, what, (double)threshold);
+    VS_REQUIRE(silence >= 0.f, "%s: silence = %g is negative (or NaN)", who, (double)silence);
     const double tmax_d = std::ceil((double)sr / (double)f0_min), tmin_d = std::floor((double)sr / (double)f0_max);
-    VS_REQUIRE(tmax_d <= YIN_MAX_TAU, "vs_f0_yin: tau_max = ceil(sr / f0_min) = %.0f exceeds %d", tmax_d, YIN_MAX_TAU);
+    VS_REQUIRE(tmax_d <= YIN_MAX_TAU, "%s: tau_max = ceil(sr / f0_min) = %.0f exceeds %d", who, tmax_d, YIN_MAX_TAU);
     const int tau_max = (int)tmax_d, tau_min = tmin_d < 2 ? 2 : (int)tmin_d;
-    VS_REQUIRE(tau_min < tau_max, "vs_f0_yin: tau_min = %d is not below tau_max = %d", tau_min, tau_max);
+    VS_REQUIRE(tau_min < tau_max, "%s: tau_min = %d is not below tau_max = %d", who, tau_min, tau_max);
     const int W = window == 0 ? 2 * tau_max : window;
-    VS_REQUIRE(W >= tau_max && W <= YIN_MAX_W, "vs_f0_yin: window = %d is not in [tau_max = %d, %d]", W, tau_max, YIN_MAX_W);
-    YinArgs a;
-    a.wav = wav, a.lengths = (const long long *)lengths, a.f0 = f0_hz, a.per = periodicity;
+    VS_REQUIRE(W >= tau_max && W <= YIN_MAX_W, "%s: window = %d is not in [tau_max = %d, %d]", who, W, tau_max, YIN_MAX_W);
     a.B = B, a.L = L, a.T = T, a.sr = sr, a.hop = hop, a.W = W, a.tau_min = tau_min, a.tau_max = tau_max;
     a.G = (tau_max + 2 + 7) / 8;                                                  // lags 0 .. tau_max + 1 in groups of eight
     a.DP = 8 * a.G;
@@ -246,8 +285,38 @@ int vs_f0_yin(const float *wav, const int64_t *lengths, int64_t B, int64_t L, in
     }
     a.F = F;
     a.n_img = (int)((one + (long long)(F - 1) * hop + 3) & ~3ll);
-    const size_t lds_bytes = sizeof(float) * ((size_t)a.K * a.n_img + (size_t)F * a.DP);
-    hipLaunchKernelGGL(yin_kernel, dim3((unsigned)ceil_div(T, F), (unsigned)(B < 65535 ? B : 65535)), dim3(YIN_THREADS), lds_bytes, as_stream(stream), a);
+    lds_bytes = sizeof(float) * ((size_t)a.K * a.n_img + (size_t)F * a.DP);
+    return VS_OK;
+}
+
+extern "C" {
+
+int vs_f0_yin(const float *wav, const int64_t *lengths, int64_t B, int64_t L, int sr, int hop, float f0_min, float f0_max, int window, float threshold,
+              float silence, float *f0_hz, float *periodicity, int64_t T, void *stream) {
+    VS_REQUIRE(wav && f0_hz, "vs_f0_yin: wav and f0_hz must not be NULL");
+    VS_REQUIRE(wav != f0_hz && wav != periodicity && f0_hz != periodicity && (const void *)lengths != (const void *)f0_hz &&
+                   (!lengths || (const void *)lengths != (const void *)periodicity),
+               "vs_f0_yin: wav, lengths, f0_hz and periodicity must be distinct buffers");
+    YinArgs a;
+    size_t lds_bytes;
+    VS_TRY(yin_setup("vs_f0_yin", "threshold", B, L, sr, hop, f0_min, f0_max, window, threshold, silence, T, a, lds_bytes));
+    a.wav = wav, a.lengths = (const long long *)lengths, a.f0 = f0_hz, a.per = periodicity, a.cand_hz = a.cand_d = nullptr;
+    hipLaunchKernelGGL(yin_kernel<false>, dim3((unsigned)ceil_div(T, a.F), (unsigned)(B < 65535 ? B : 65535)), dim3(YIN_THREADS), lds_bytes, as_stream(stream), a);
+    VS_CHECK_HIP(hipGetLastError());
+    return VS_OK;
+}
+
+int vs_f0_candidates(const float *wav, const int64_t *lengths, int64_t B, int64_t L, int sr, int hop, float f0_min, float f0_max, int window, float gate,
+                     float silence, float *cand_hz, float *cand_d, int64_t T, void *stream) {
+    VS_REQUIRE(wav && cand_hz && cand_d, "vs_f0_candidates: wav, cand_hz and cand_d must not be NULL");
+    VS_REQUIRE(wav != cand_hz && wav != cand_d && cand_hz != cand_d && (const void *)lengths != (const void *)cand_hz && (const void *)lengths != (const void *)cand_d,
+               "vs_f0_candidates: wav, lengths, cand_hz and cand_d must be distinct buffers");
+    YinArgs a;
+    size_t lds_bytes;
+    VS_TRY(yin_setup("vs_f0_candidates", "gate", B, L, sr, hop, f0_min, f0_max, window, gate, silence, T, a, lds_bytes));
+    VS_REQUIRE(B <= INT64_MAX / T / 8, "vs_f0_candidates: B * T * 8 is out of range (B = %lld, T = %lld)", (long long)B, (long long)T);
+    a.wav = wav, a.lengths = (const long long *)lengths, a.f0 = a.per = nullptr, a.cand_hz = cand_hz, a.cand_d = cand_d;
+    hipLaunchKernelGGL(yin_kernel<true>, dim3((unsigned)ceil_div(T, a.F), (unsigned)(B < 65535 ? B : 65535)), dim3(YIN_THREADS), lds_bytes, as_stream(stream), a);
     VS_CHECK_HIP(hipGetLastError());
     return VS_OK;
 }

@@ -244,7 +244,7 @@ OPTIONS = dict(
     limit=((), tuple(limiter.DEFAULTS), lambda o, hop_size: limiter.check_args(**o)),
     guide_correct=((), ("midi_of_token", "offset_cents", *guide_correct_ops.DEFAULTS), lambda o, hop_size: _check_guide_op(o, guide_correct_ops, True)),
     guide_align=((), ("midi_of_token", "offset_cents", *guide_align_ops.DEFAULTS), lambda o, hop_size: _check_guide_op(o, guide_align_ops, False)),
-    guide_track=(("sample_rate",), ("sample_rate", "recording_rate", "f0_min", "f0_max", "window", "threshold", "silence"), _check_track))
+    guide_track=(("sample_rate",), ("sample_rate", "recording_rate", "f0_min", "f0_max", "window", "threshold", "silence", "path"), _check_track))
 
 
 def _option(name, given, hop_size=None):
@@ -270,6 +270,9 @@ def guide_items(items, hop_size, device, max_frames_per_batch=32768, fit=True, l
     level: None, or the half width of dynamics.track_level (an integer in [0, 8]): each bucket's loudness contour is then tracked from the same device tensor
     the pitch is (after the rate conversion), fitted exactly as the f0 curve is and stored as the item's "level" -- fp32 mean-square power per
     frame, 0 = no level.  An item that brings its own "level" keeps it.
+    track["path"]: None, or a dict of pitch_track.PATH_DEFAULTS keys (possibly empty): the curve is then the cheapest path through every frame's lag candidates
+    (extract_f0(path=)) instead of a decision per frame -- no octave jumps on a weak fundamental, no flicker of the voicing; a recording may
+    then have at most 32768 frames (ValueError naming the item).
     As synthesize's first pre-pass (guide_track: a dict of these keywords), on copies of the items: tempo and "ph_stretch" warp a tracked curve as they warp a given
     one; fit=False under guide_align, level = guide_dynamics' half_width.  "guide_wav" without guide_track: ValueError; no "guide_wav": guide_track is not looked at.
     ValueError: no sample_rate, an unknown keyword, a rate that is no integer >= 1 or that the converter's table budget does not admit, an item with both "f0" and "guide_wav", a
@@ -295,6 +298,10 @@ def guide_items(items, hop_size, device, max_frames_per_batch=32768, fit=True, l
         wavs[i] = w.astype(np.float32, copy=False)
     out = [dict(it) for it in items]
     samples = {i: resample.out_length(len(w), rates[i], sr) for i, w in wavs.items()}          # at the model's rate
+    if track.get("path") is not None:
+        for i, n in samples.items():
+            if n // hop_size > pitch_track.PATH_FRAMES_LIMIT:
+                raise ValueError(f"item {i}: guide_wav has {n // hop_size} frames; path tracking takes at most {pitch_track.PATH_FRAMES_LIMIT} (split the recording)")
     buckets = [idx for r in sorted(set(rates.values()))               # (recordings of one rate share a bucket)
                for idx in _buckets({i: n // hop_size for i, n in samples.items() if rates[i] == r}, max_frames_per_batch)]
     for idx in buckets:
@@ -564,6 +571,7 @@ def synthesize(model, items, hop_size, max_frames_per_batch=32768, noise_scale=1
     graphs and trimming see the new lengths and curves -- then three stages behind the generator, on the batch's own stream.  Each option is None (nothing changes, nothing is launched) or a dict, checked through OPTIONS before the model is looked at and before any launch
     (ValueError), in the order resample_to, guide_dynamics, limit, guide_correct, guide_align, guide_track.
       1. guide_track      the pitch (and level) curve of an item's recording "guide_wav" is tracked     -> guide_items
+                          (with "path": {...} as a Viterbi path through every frame's lag candidates, pitch_track.extract_f0(path=))
       2. guide_align      the score is timed to the guide curve                                          -> align_items
       3. guide_correct    the guide curve is pulled onto the score                                       -> correct_items
       4. tempo            and an item's "ph_stretch": the alignment is retimed, the curves warped        -> retime_items
