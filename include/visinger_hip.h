@@ -660,6 +660,47 @@ VS_API int vs_f0_path(const float *cand_hz, const float *cand_d, const int64_t *
                       int w_jump, int jump_cap, int reserved, float *f0_hz, int32_t *state, int32_t *cost, void *stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * f13 vibrato (csrc/vibrato.hip): a per-note pitch modulation ADDED to the curve the model sings -- the predictor's own curve or a guide --
+ *     between the pitch predictor and vs_pitch_condition.  Not in the reference.  f8 keeps, scales or removes the vibrato a recording has; nothing else adds one.
+ *     Unit: 1/16 cent; 19200 units are an octave.  The offset is integer arithmetic on a host-built sine table: the device evaluates no transcendental function
+ *     for it.  vs_pitch_condition and vs_f0_norm_interp are unchanged: the modulated curve goes into vs_pitch_condition as its f0_norm (with pred beside it when
+ *     the voicing is the model's), so a transposition in cents moves the modulated curve and f0_hz_out shows it.
+ *     vs_pitch_vibrato: curve fp32, read with an element stride of 1 (a normalised curve [B, T]) or 2 (column 0 of the predictor's [B, T, 2]), values in the
+ *       model's domain log2(Hz + 1);  mel2ph int64 [B, T], read clamped to [0, T_ph], 0 = padding;  lengths DEVICE int64 [B], clamped to [0, T], or NULL (= T): Lr;
+ *       note_of_token int32 [B, T_ph]: the note a token belongs to, 0 = no note (a rest);  note_depth_q int32 [B, T_ph] or NULL: the depth of a note in units, read
+ *       at the note's FIRST token, negative (-1) = the item's;  params int32 [B, VS_VIBRATO_PARAMS]: depth_q, inc, delay, attack, release, min_len per item;
+ *       sine int32 [VS_VIBRATO_SINE + 1]: round(16384 sin(2 pi i / 1024)), built on the host in double: part of the input.
+ *       depth_q in [0, VS_VIBRATO_MAX_DEPTH_Q] units (one octave);  inc: the phase step per frame in 2^-32 cycles, taken as uint32 (the host makes it as
+ *       round(rate_hz hop / sample_rate 2^32));  delay and min_len in [0, VS_VIBRATO_MAX_DELAY] frames;  attack and release in [1, VS_VIBRATO_MAX_RAMP] frames.
+ *       The ranges cannot be checked on the device without a readback: they are the caller's to keep (the Python layer does), and a value outside is CLAMPED to
+ *       its range, a note_depth_q above the maximum to the maximum: nothing out of range can fault.
+ *       Per frame t < Lr:  n[t] = note_of_token[mel2ph[t] - 1], 0 where mel2ph[t] = 0.  start[t] = the last s <= t with s == 0 or n[s] != n[s - 1];
+ *       end[t] = the first e > t with e == Lr or n[e] != n[e - 1].  len = end - start, p = t - start - delay, rem = end - 1 - t;  depth = the note's
+ *       (note_depth_q at token mel2ph[start] - 1) when that is >= 0, else depth_q.
+ *       offset_q[t] = 0 where n[t] == 0, len < min_len, p < 0 or depth == 0.  Otherwise, in integers:
+ *         ph = (uint32)(inc * (uint32) p);  i = ph >> 22;  f = (ph >> 6) & 0xFFFF;  s = sine[i] + (((sine[i + 1] - sine[i]) * f) >> 16)  (arithmetic shift: floor);
+ *         ea = min(p, attack);  er = min(rem + 1, release);  v = (int64) depth * s * ea * er;  den = 16384 * attack * release;
+ *         offset_q[t] = sign(v) * ((|v| + den / 2) / den).
+ *       |v| <= 19200 * 16384 * 4096^2 < 2^63, and |offset_q| <= depth.  The first modulated frame of a note is 0 (ea = 0): the vibrato fades in over `attack`
+ *       frames behind the delay and out over the last `release` frames of the note.
+ *       curve_out[t] = the bits of curve[t] where offset_q[t] == 0;  elsewhere log2f((exp2f(x) - 1) * exp2f((float) offset_q / 19200.0f) + 1), the accurate
+ *       exp2f / log2f: the composition vs_pitch_condition uses for its cents.  For t >= Lr: offset_q = 0, curve_out = 0.  Every element of both is written.
+ *       A frame's result depends on its own row's frames only: not on B, the row index or T.
+ *       One launch: one workgroup per row (grid-strided), chunks of 256 frames walked right to left for `end` (parked in offset_q) and left to right for `start`,
+ *       the boundary carried from chunk to chunk in a register, as in vs_f0_norm_interp: a note may span any number of chunks.
+ *       VS_EINVAL before anything is launched: a NULL buffer other than lengths / note_depth_q, B, T, T_ph <= 0, T or T_ph >= 2^31, a stride other than 1 or 2,
+ *       a stride-2 curve that is not 8-byte aligned, B T out of range, curve / offset_q / curve_out not three buffers.  No workspace, no allocation, no atomics,
+ *       no host synchronisation; every input is read on the device: a captured graph replays under other settings by overwriting params.                  */
+#define VS_VIBRATO_PARAMS 6
+#define VS_VIBRATO_SINE 1024
+#define VS_VIBRATO_MAX_DEPTH_Q 19200
+#define VS_VIBRATO_MAX_RAMP 4096
+#define VS_VIBRATO_MAX_DELAY 65535
+VS_API int vs_pitch_vibrato(const float *curve, int curve_stride, const int64_t *mel2ph, const int64_t *lengths, const int32_t *note_of_token,
+                            const int32_t *note_depth_q, const int32_t *params, const int32_t *sine, int32_t *offset_q, float *curve_out, int64_t B, int64_t T,
+                            int64_t T_ph, void *stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * a13 grouped / strided Conv1d of the scale discriminator (modules/discriminator.py:55-60) and its gradients.
  *     x: [B, c_in, T], w: [c_out, c_in/groups, k], y / gy: [B, c_out, T_out], T_out = (T + 2*pad - k)/stride + 1.
  *     vs_gconv1d_bwd_weight writes one plane per batch item, gw_planes [B][c_out, c_in/groups, k]; gw = their sum.

@@ -129,6 +129,7 @@ def lib():
     L.vs_prior_sample.argtypes = [_f32p, _f32p, i64, _f32p, vp, i64, i64, cf, _f32p, _f32p, i64, i64, i64, vp]
     L.vs_f0_norm_interp.argtypes = [_f32p, vp, _f32p, _f32p, i64, i64, vp]
     L.vs_pitch_condition.argtypes = [_f32p, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p, i64, i64, vp]
+    L.vs_pitch_vibrato.argtypes = [_f32p, ci, vp, vp, vp, vp, vp, vp, vp, _f32p, i64, i64, i64, vp]
     L.vs_retime_tokens.argtypes = [vp, vp, _f32p, _f32p, i64, i64, vp, vp, vp, i64, i64, i64, vp]
     L.vs_retime_frames.argtypes = [vp, vp, vp, _f32p, i64, vp, _f32p, i64, i64, i64, vp]
     L.vs_f0_yin.argtypes = [_f32p, vp, i64, i64, ci, ci, cf, cf, ci, cf, cf, _f32p, _f32p, i64, vp]

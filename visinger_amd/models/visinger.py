@@ -16,6 +16,9 @@ Pitch control (not in the reference; visinger_amd/pitch.py): ``f0
 and gap-interpolated on the device; ``voicing`` takes the voiced frames from the guide or from the predictor; ``pitch_shift_cents`` transposes
 the conditioning curve per item; ``ret["f0_hz"]`` is then the curve the prior was conditioned on, in Hz.
 
+Vibrato (not in the reference; visinger_amd/vibrato.py): ``vibrato`` -- the int32 [B, 6] settings ``vibrato.params`` makes -- adds a per-note
+modulation to the conditioning curve (predicted or guided) on the device, before the transposition; ``ret["vibrato_q"]`` is the offset in 1/16 cent.
+
 Tempo control (not in the reference; visinger_amd/timing.py): ``tempo`` (per item) and ``ph_stretch`` (per token) retime ``mel2ph`` on the
 device before anything else runs, and warp ``f0_hz`` along with it; ``ret["mel2ph"]`` / ``ret["frame_lengths"]`` are the alignment that was sung.
 """
@@ -25,6 +28,7 @@ import torch
 import torch.nn as nn
 
 from .. import pitch, sampling, timing
+from .. import vibrato as vibrato_ops
 from ..modules.commons.utils import Embedding, rand_slice_segments, slice_segments
 from ..modules.discriminator import DiscriminatorP, DiscriminatorS
 from ..modules.rel_transformer import SinusoidalPositionalEmbedding
@@ -132,8 +136,14 @@ class VISinger(nn.Module):
 
     def forward(self, text_tokens, pitch_tokens, dur_tokens, mel2ph, spk_embed=None, spk_id=None, f0=None, uv=None,
                 mel=None, infer=False, noise=None, noise_q=None, u_slice=None, mask_decoder=False, seeds=None, takes=1, first_take=0,
-                noise_scale=1.0, f0_hz=None, voicing="guide", pitch_shift_cents=None, tempo=None, ph_stretch=None, max_frames=None, **kwargs):
-        """tempo / ph_stretch / max_frames (synthesis only): mel2ph is retimed on the device by ph_stretch[b, i] / tempo[b] per token (timing.retime; tempo: a
+                noise_scale=1.0, f0_hz=None, voicing="guide", pitch_shift_cents=None, tempo=None, ph_stretch=None, max_frames=None, vibrato=None,
+                note_of_token=None, note_depth_q=None, **kwargs):
+        """vibrato / note_of_token / note_depth_q (synthesis only; needs use_pitch_embed): vibrato is the int32 GPU tensor [B, 6] of vibrato.params; the curve
+        that conditions the prior -- the predictor's, or the guide's -- is modulated note by note on the device (vibrato.vibrato) after any retiming, on the
+        retimed mel2ph, and before pitch_shift_cents transposes it; ret["f0_hz"] shows the modulated curve and ret["vibrato_q"] is the offset, int32 [B, T] in 1/16
+        cent.  note_of_token: int32 [B, T_ph], the note of every token, 0 = a rest; None = vibrato.notes_of_tokens(pitch_tokens), made on the device.
+        note_depth_q: None or int32 [B, T_ph], a depth per note (read at its first token), -1 = the item's.  None = nothing is launched.
+        tempo / ph_stretch / max_frames (synthesis only): mel2ph is retimed on the device by ph_stretch[b, i] / tempo[b] per token (timing.retime; tempo: a
         number, one per item, or an fp32 GPU tensor [B]; ph_stretch: fp32 [B, T_ph]) and f0_hz, a curve on the old timeline, is warped with it; the step then runs
         on the retimed alignment.  max_frames: the frame capacity of the result (items are cut at it, nothing is read back on the host: graph-capturable);
         None = the longest retimed item, one host synchronisation.  An injected `noise` must have the new frame count; dur_tokens stay the caller's."""
@@ -146,6 +156,16 @@ class VISinger(nn.Module):
             if not self.hparams["use_pitch_embed"]:
                 raise ValueError("f0_hz / voicing / pitch_shift_cents need a model with use_pitch_embed: this one has no pitch condition")
             pitch_edit = (f0_hz, voicing, pitch_shift_cents)
+        if vibrato is not None:
+            if not self.hparams["use_pitch_embed"]:
+                raise ValueError("vibrato needs a model with use_pitch_embed: this one has no pitch condition")
+            if not infer:
+                raise ValueError("vibrato applies to the synthesis path only (infer=True)")
+            if note_of_token is None:
+                note_of_token = vibrato_ops.notes_of_tokens(pitch_tokens)
+            pitch_edit = (f0_hz, voicing, pitch_shift_cents, (vibrato, note_of_token, note_depth_q))
+        elif note_of_token is not None or note_depth_q is not None:
+            raise ValueError("note_of_token / note_depth_q belong to vibrato: give vibrato (vibrato.params)")
         if seeds is not None:
             if noise is not None:
                 raise ValueError("seeds and noise are two sources of the same sample: give one of them")
@@ -163,7 +183,7 @@ class VISinger(nn.Module):
                                                                 max_frames=max_frames, curve=f0_hz)
             ret["mel2ph"] = mel2ph
             if pitch_edit is not None:
-                pitch_edit = (f0_hz, voicing, pitch_shift_cents)
+                pitch_edit = (f0_hz,) + pitch_edit[1:]
         elif max_frames is not None:
             raise ValueError("max_frames is the frame capacity of a retimed call: give tempo or ph_stretch")
         frame_mask, spk, mu_p, logs_p = self._prior(text_tokens, pitch_tokens, dur_tokens, mel2ph, spk_embed, spk_id, f0, uv, ret, pitch_edit)
@@ -197,12 +217,14 @@ class VISinger(nn.Module):
             voiced = uv == 0
         return (f0 * voiced).unsqueeze(1) * tgt_nonpadding
 
-    def forward_pitch_edit(self, pitch_inp, f0, uv, spk_emb, tgt_nonpadding, mel2ph, ret, f0_hz, voicing, cents):
+    def forward_pitch_edit(self, pitch_inp, f0, uv, spk_emb, tgt_nonpadding, mel2ph, ret, f0_hz, voicing, cents, vibrato=None):
         """forward_pitch under pitch control: the predictor runs as always (ret["f0_pred"]); the condition comes from one launch
         (pitch.pitch_condition) on the guide curve f0_hz (Hz, 0 = unvoiced; normalised and gap-interpolated on the device over each item's
         own frames, pitch.norm_interp_f0), on the teacher-forced f0 / uv, or on the predicted curve -- transposed by `cents` per item.
         voicing="guide": voiced where the guide is (equal to the reference's forward(f0=, uv=) on its own norm_interp_f0 of the item);
-        "model": the interpolated guide under the predictor's voicing.  ret["f0_hz"]: the curve that conditions the prior, in Hz."""
+        "model": the interpolated guide under the predictor's voicing.  ret["f0_hz"]: the curve that conditions the prior, in Hz.
+        vibrato: None or (params, note_of_token, note_depth_q) -- the curve, whichever it is, is modulated per note (vibrato.vibrato, one launch) in front of the
+        condition, which then takes it as its f0_norm (with the predictor's pair beside it where the voicing is the model's); ret["vibrato_q"]: the offset."""
         scale = self.hparams["predictor_grad"]
         if scale != 1:
             stopped = pitch_inp.detach()
@@ -213,6 +235,10 @@ class VISinger(nn.Module):
             f0, uv = pitch.norm_interp_f0(f0_hz, lengths)
             if voicing == "model":
                 uv = None
+        if vibrato is not None:
+            prm, note_of_token, note_depth_q = vibrato
+            curve = dict(pred=pred) if f0 is None else dict(curve=f0)
+            f0, ret["vibrato_q"] = vibrato_ops.vibrato(curve.get("curve"), mel2ph, note_of_token, prm, note_depth_q=note_depth_q, pred=curve.get("pred"))
         # (the voicing decision carries no gradient, and a given curve is data: only a SHIFTED PREDICTED curve would need a backward)
         src = None if (f0 is not None and uv is not None) else (pred.detach() if f0 is not None else pred)
         cond, ret["f0_hz"] = pitch.pitch_condition(tgt_nonpadding, pred=src, f0_norm=f0, uv=uv, cents=cents, return_hz=True)

@@ -10,6 +10,7 @@ from . import dynamics
 from . import guide_align as guide_align_ops
 from . import guide_correct as guide_correct_ops
 from . import limiter, pitch, pitch_track, resample, sampling, timing
+from . import vibrato as vibrato_ops
 
 
 def bucket_by_length(lengths, max_frames_per_batch, max_items_per_batch=256, keys=None):
@@ -143,7 +144,9 @@ class GraphedStep:
     Tempo control: tempo= (anything timing.factor_tensor takes) and ph_stretch= (fp32 [B, T_ph]) become static device buffers the retiming kernels read,
     overwritten by __call__(tempo=, ph_stretch=); max_frames is required with either: the frame capacity fixed by the capture (the step runs max_frames
     frames wide, an item is cut at it, `noise` has that many frames).  `frame_lengths_out` is the static int64 [B] buffer of the retimed lengths and
-    `mel2ph_out` the retimed alignment."""
+    `mel2ph_out` the retimed alignment.
+    Vibrato: vibrato= (the int32 [B, 6] tensor of vibrato.params) becomes a static buffer the vibrato kernel reads, overwritten by __call__(vibrato=); a batch's
+    "note_of_token" / "note_depth_q" sit among the static inputs like the tokens.  `vibrato_q_out` is the static int32 [B, T] buffer of the offsets."""
 
     @staticmethod
     def fingerprint(model):
@@ -153,12 +156,14 @@ class GraphedStep:
 
     # the optional static control buffers: attribute -> the device tensor of a value, for a step of B items of T_ph tokens
     CONTROLS = dict(seeds=lambda v, B, T_ph, dev: sampling.seeds_tensor(v), cents=lambda v, B, T_ph, dev: pitch.cents_tensor(v, B, dev),
-                    tempo=lambda v, B, T_ph, dev: timing.factor_tensor(v, B, dev), ph_stretch=timing.stretch_tensor)
+                    tempo=lambda v, B, T_ph, dev: timing.factor_tensor(v, B, dev), ph_stretch=timing.stretch_tensor,
+                    vibrato=lambda v, B, T_ph, dev: vibrato_ops.params_tensor(v, B, dev))
     # what a replay is told whose optional inputs are not the capture's, in the order they are compared
     _SAMPLE = "a graph captured with noise is replayed with noise, one captured with seeds with seeds"
     _PITCH = "a graph is replayed with the inputs it was captured with (guide curve and pitch shift included)"
     _TEMPO = "a graph captured with a tempo / token stretch is replayed with one (and one captured without, without)"
-    REFUSALS = dict(seeds=_SAMPLE, noise=_SAMPLE, f0_hz=_PITCH, cents=_PITCH, tempo=_TEMPO, ph_stretch=_TEMPO)
+    _VIBRATO = "a graph captured with vibrato settings is replayed with some (and one captured without, without)"
+    REFUSALS = dict(seeds=_SAMPLE, noise=_SAMPLE, f0_hz=_PITCH, cents=_PITCH, tempo=_TEMPO, ph_stretch=_TEMPO, vibrato=_VIBRATO)
 
     def _controls(self, **given):
         """{attribute: device tensor, or None where no value is given}"""
@@ -166,7 +171,7 @@ class GraphedStep:
         return {k: None if given[k] is None else make(given[k], *size) for k, make in self.CONTROLS.items()}
 
     def __init__(self, model, batch, noise, mask_decoder, seeds=None, takes=1, first_take=0, noise_scale=1.0, voicing="guide", cents=None, tempo=None,
-                 ph_stretch=None, max_frames=None):
+                 ph_stretch=None, max_frames=None, vibrato=None):
         if seeds is not None and noise is not None:
             raise ValueError("seeds and noise are two sources of the same sample: give one of them")
         if (tempo is not None or ph_stretch is not None) != (max_frames is not None):
@@ -174,12 +179,14 @@ class GraphedStep:
         self.weights = self.fingerprint(model)       # a replay never re-folds / re-packs weights: the graph is only valid for these
         self.static = {k: v.clone() for k, v in batch.items()}
         self.noise = None if seeds is not None else noise.clone()
-        for k, t in self._controls(seeds=seeds, cents=cents, tempo=tempo, ph_stretch=ph_stretch).items():
+        for k, t in self._controls(seeds=seeds, cents=cents, tempo=tempo, ph_stretch=ph_stretch, vibrato=vibrato).items():
             setattr(self, k, None if t is None else t.clone())
         sample = dict(noise=self.noise) if seeds is None else dict(seeds=self.seeds, takes=takes, first_take=first_take, noise_scale=noise_scale)
-        self.f0_hz_out = self.frame_lengths_out = self.mel2ph_out = None
+        self.f0_hz_out = self.frame_lengths_out = self.mel2ph_out = self.vibrato_q_out = None
         if "f0_hz" in batch or self.cents is not None:
             sample.update(f0_hz=self.static.get("f0_hz"), voicing=voicing, pitch_shift_cents=self.cents)
+        if self.vibrato is not None:
+            sample.update(vibrato=self.vibrato, note_of_token=self.static.get("note_of_token"), note_depth_q=self.static.get("note_depth_q"))
         if max_frames is not None:
             sample.update(tempo=self.tempo, ph_stretch=self.ph_stretch, max_frames=int(max_frames))
 
@@ -187,7 +194,7 @@ class GraphedStep:
             b = self.static
             ret = model(b["text_tokens"], b["pitch_tokens"], b["dur_tokens"], b["mel2ph"], spk_id=b["spk_id"], infer=True,
                         mask_decoder=mask_decoder, **sample)
-            self.f0_hz_out = ret.get("f0_hz")
+            self.f0_hz_out, self.vibrato_q_out = ret.get("f0_hz"), ret.get("vibrato_q")
             self.frame_lengths_out, self.mel2ph_out = ret.get("frame_lengths"), ret.get("mel2ph")
             return ret["wav_out"]
 
@@ -200,8 +207,8 @@ class GraphedStep:
         with torch.cuda.graph(self.graph):
             self.out = run()
 
-    def __call__(self, batch, noise, seeds=None, cents=None, tempo=None, ph_stretch=None):
-        given = dict(noise=noise, f0_hz=batch.get("f0_hz"), seeds=seeds, cents=cents, tempo=tempo, ph_stretch=ph_stretch)
+    def __call__(self, batch, noise, seeds=None, cents=None, tempo=None, ph_stretch=None, vibrato=None):
+        given = dict(noise=noise, f0_hz=batch.get("f0_hz"), seeds=seeds, cents=cents, tempo=tempo, ph_stretch=ph_stretch, vibrato=vibrato)
         for k, refusal in self.REFUSALS.items():
             if (given[k] is None) != ((self.static.get(k) if k == "f0_hz" else getattr(self, k)) is None):
                 raise ValueError(refusal)
@@ -256,6 +263,27 @@ def _option(name, given, hop_size=None):
             raise ValueError(f"{name} must contain {' and '.join(required)}, got {sorted(opts)}")
         check(opts, hop_size)
     return opts
+
+
+def _check_vibrato(given, hop_size, items, model):
+    """the check of synthesize(vibrato=): a dict of vibrato.DEFAULTS keys -- each a number or one value per item -- plus the required sample_rate; the items'
+    "note_of_token" and "vibrato_depth_cents" hold one value per token; the model has a pitch condition.  Returns (the six integers of every item, {item index:
+    its note_depth_q row} for the items with "vibrato_depth_cents"); ValueError otherwise.  Checked on its own, not through OPTIONS: that table's order is
+    the order of the first refusals of a call, which this option leaves as it is."""
+    opts = A.keys("vibrato", given, ("sample_rate", *vibrato_ops.DEFAULTS))
+    if "sample_rate" not in opts:
+        raise ValueError(f"vibrato must contain sample_rate (the model's), got {sorted(opts)}")
+    rows = vibrato_ops.params_rows(len(items), opts.pop("sample_rate"), hop_size, **opts)
+    depths = {}
+    for i, it in enumerate(items):
+        for key in ("note_of_token", "vibrato_depth_cents"):
+            if it.get(key) is not None and np.shape(it[key]) != (len(it["text_tokens"]),):
+                raise ValueError(f"item {i}: {key} has {np.shape(it[key])} values for {len(it['text_tokens'])} tokens (one per token)")
+        if it.get("vibrato_depth_cents") is not None:
+            depths[i] = vibrato_ops.depth_q_of_tokens(it["vibrato_depth_cents"])
+    if not getattr(model, "hparams", {}).get("use_pitch_embed"):
+        raise ValueError("vibrato needs a model with use_pitch_embed: this one has no pitch condition")
+    return rows, depths
 
 
 def guide_items(items, hop_size, device, max_frames_per_batch=32768, fit=True, level=None, **track):
@@ -528,7 +556,7 @@ class PostChain:
 @torch.no_grad()
 def synthesize(model, items, hop_size, max_frames_per_batch=32768, noise_scale=1.0, generator=None, equal_tokens=False,
                graphs=None, streams=2, seeds=None, takes=1, first_take=0, voicing="guide", pitch_shift_cents=None, return_f0=False,
-               tempo=None, guide_track=None, guide_align=None, guide_correct=None, resample_to=None, guide_dynamics=None, limit=None):
+               tempo=None, guide_track=None, guide_align=None, guide_correct=None, resample_to=None, guide_dynamics=None, limit=None, vibrato=None):
     """Run VISinger.forward(infer=True) over length-bucketed batches.  Returns a list of float32 waveforms trimmed to
     each item's own length (frames * hop_size), in the input order.
 
@@ -567,6 +595,12 @@ def synthesize(model, items, hop_size, max_frames_per_batch=32768, noise_scale=1
     conditioning curve (guide or predicted), read on the device.  return_f0: the result is a list of (wav, f0_hz) with f0_hz the float32 curve the prior was
     conditioned on, in Hz (0 = unvoiced), trimmed to the item's frames.  Items without "f0" in a call without these arguments run exactly as before.
 
+    Vibrato (VISinger.forward vibrato=, visinger_amd/vibrato.py; needs use_pitch_embed): vibrato is None or a dict of vibrato.DEFAULTS keys
+    (depth_cents, rate_hz, delay_s, attack_s, release_s, min_note_s: a number, or one per item in input order) plus the required sample_rate, the model's.  The
+    curve every item is sung on -- predicted or guided -- then gets a per-note modulation on the device, in front of the transposition; return_f0 shows it.  An
+    item may carry "note_of_token" (one note id per token, 0 = a rest; default: vibrato.notes_of_tokens of its pitch tokens) and "vibrato_depth_cents" (one depth
+    per token, read at a note's first token; NaN or None = the call's depth_cents).  Checked next to `voicing`, behind the option dicts below.
+
     The controls, in the order their stages run: four pre-passes on the device, on copies of the items -- the call runs on what they leave, so buckets, `ragged`,
     graphs and trimming see the new lengths and curves -- then three stages behind the generator, on the batch's own stream.  Each option is None (nothing changes, nothing is launched) or a dict, checked through OPTIONS before the model is looked at and before any launch
     (ValueError), in the order resample_to, guide_dynamics, limit, guide_correct, guide_align, guide_track.
@@ -598,6 +632,9 @@ def synthesize(model, items, hop_size, max_frames_per_batch=32768, noise_scale=1
         items = retime_items(items, tempo, device, max_frames_per_batch)
     if voicing not in ("guide", "model"):
         raise ValueError(f"voicing must be 'guide' or 'model', got {voicing!r}")
+    vib_rows = vib_depths = None
+    if vibrato is not None:
+        vib_rows, vib_depths = _check_vibrato(vibrato, hop_size, items, model)
     if pitch_shift_cents is not None:
         pitch_shift_cents = pitch.cents_tensor(pitch_shift_cents, len(items), "cpu").tolist()      # (checked here; a batch's values travel with the batch)
     if seeds is not None:
@@ -651,18 +688,33 @@ def synthesize(model, items, hop_size, max_frames_per_batch=32768, noise_scale=1
             cents_dev = pitch.cents_tensor([pitch_shift_cents[i] for i in idx] if pitch_shift_cents is not None else 0.0, B, device)
             record.append(cents_dev)
             pitch_kw = dict(f0_hz=batch.get("f0_hz"), voicing=voicing, pitch_shift_cents=cents_dev)
+        # vibrato: the six settings of every item, and the notes / per-note depths only where an item of the batch carries its own
+        vib_dev = None
+        if vib_rows is not None:
+            T_ph = batch["text_tokens"].shape[1]
+            vib_dev = torch.tensor([vib_rows[i] for i in idx], dtype=torch.int32).to(device)
+            if any(items[i].get("note_of_token") is not None for i in idx):
+                notes = [items[i]["note_of_token"] if items[i].get("note_of_token") is not None else
+                         vibrato_ops.notes_of_tokens(np.asarray(items[i]["pitch_tokens"])).numpy() for i in idx]
+                batch["note_of_token"] = _pad_rows(notes, torch.int32, T_ph).to(device)
+            if any(i in vib_depths for i in idx):
+                batch["note_depth_q"] = _pad_rows([vib_depths.get(i, ()) for i in idx], torch.int32, T_ph, fill=-1).to(device)
+            record += [vib_dev] + [batch[k] for k in ("note_of_token", "note_depth_q") if k in batch]
+            pitch_kw = dict(pitch_kw, vibrato=vib_dev, note_of_token=batch.get("note_of_token"), note_depth_q=batch.get("note_depth_q"))
         post, post_tensors = chain.batch([lengths[i] for i in idx], [items[i].get("level") for i in idx], T, device)
         record += post_tensors
 
         if graphs is not None:
             key = (B, batch["text_tokens"].shape[1], T, ragged) + key_tail + ("f0_hz" in batch, voicing, cents_dev is not None)
+            if vib_dev is not None:
+                key += ("vibrato", "note_of_token" in batch, "note_depth_q" in batch)
             if key not in graphs or graphs[key].weights != GraphedStep.fingerprint(model):      # (re-captured after a weight update)
-                graphs[key] = GraphedStep(model, batch, noise, ragged, voicing=voicing, cents=cents_dev,
+                graphs[key] = GraphedStep(model, batch, noise, ragged, voicing=voicing, cents=cents_dev, vibrato=vib_dev,
                                           **{k: v for k, v in sample.items() if k != "noise"})
 
         def run():                                   # (called in this iteration, at once: it sees this batch's variables)
             if graphs is not None:                   # (the post chain runs behind the replay, outside the capture)
-                return post(graphs[key](batch, noise, seeds=seeds_dev, cents=cents_dev)), graphs[key].f0_hz_out
+                return post(graphs[key](batch, noise, seeds=seeds_dev, cents=cents_dev, vibrato=vib_dev)), graphs[key].f0_hz_out
             ret = model(batch["text_tokens"], batch["pitch_tokens"], batch["dur_tokens"], batch["mel2ph"],
                         spk_id=batch["spk_id"], infer=True, mask_decoder=ragged, **sample, **pitch_kw)
             return post(ret["wav_out"]), ret.get("f0_hz")
