@@ -701,6 +701,48 @@ VS_API int vs_pitch_vibrato(const float *curve, int curve_stride, const int64_t 
                             int64_t T_ph, void *stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * f14 loudness normalisation (csrc/loudness.hip): the integrated programme loudness of every row of a batch of ragged waveforms -- mono ITU-R
+ *     BS.1770-4 / EBU R128: K-weighted, gated, in LUFS -- and the gain that brings the row to a target.  Not in the reference (it peak-normalises on the host).
+ *     wav fp32 [B, L] at sr Hz, sr an integer in [VS_LOUD_MIN_RATE, VS_LOUD_MAX_RATE] divisible by 10;  s = sr / 10 samples a step (100 ms);  lengths DEVICE
+ *     int64 [B], clamped to [0, L], or NULL (= L): n.  Three entries, three launches, nothing read back in between.
+ *     1. K-weighting.  Two biquads in cascade, b / a with a[0] = 1, made by the HOST in double from the rate (the bilinear transform of the standard's analogue
+ *        prototypes, which gives the standard's 48 kHz table to the printed digits), K = tan(pi f0 / sr), a0 = 1 + K / Q + K^2:
+ *          shelf      f0 = 1681.974450955533, G = 3.999843853973347 dB, Q = 0.7071752369554196;  Vh = 10^(G / 20), Vb = Vh^0.4996667741545416;
+ *                     b = [(Vh + Vb K / Q + K^2) / a0, 2 (K^2 - Vh) / a0, (Vh - Vb K / Q + K^2) / a0],  a = [1, 2 (K^2 - 1) / a0, (1 - K / Q + K^2) / a0]
+ *          high-pass  f0 = 38.13547087602444, Q = 0.5003270373238773;  b = [1, -2, 1],  a = [1, 2 (K^2 - 1) / a0, (1 - K / Q + K^2) / a0].
+ *        Each in transposed direct form II, in fp64, from a zero state at the row's first sample:  y = b0 x + z1;  z1 = b1 x - a1 y + z2;  z2 = b2 x - a2 y.
+ *     2. Steps.  NS = the width of S.  Step i < min(n / s, NS) is the samples i s .. i s + s - 1;  S[b, i] = the fp64 sum of the squares of its weighted samples in
+ *        a fixed order (lane l of 256 its c = ceil(s / 256) consecutive samples ascending, then a butterfly over the wave's 64 lanes, then the four waves);
+ *        every other element of S is 0.  Only complete steps inside the row count.
+ *        vs_loud_steps: coef HOST double [10]: b0 b1 b2 a1 a2 of the shelf, then of the high-pass;  carry DEVICE double [8, 2, 16]: with A the 4 x 4 transition of
+ *        the cascade's state (z1, z2, z1', z2') over one sample of zero input and M = A^c, carry[k] is M^(2^k) row major as a pair (the exact power of A's doubles
+ *        rounded once, and what that rounding left), built on the host: part of the input.  One workgroup per row walks the steps;  the state in front of every
+ *        lane's samples comes from a log-step scan of the lanes' zero-state end states with these matrices, formed in pairs of doubles and rounded once per level.
+ *        The result differs from the serial filter's by rounding only: the bound is derived in DESIGN.md 4.21.
+ *     3. Blocks and gates (vs_loud_gate), fp64, the sums in a fixed order.  Block j < max(0, min(n / s, NS) - 3) is the steps j .. j + 3 (400 ms, 75 % overlap):
+ *        z_j = (((S_j + S_(j+1)) + S_(j+2)) + S_(j+3)) / (4 s).  Absolute gate: z_j > VS_LOUD_ABS_GATE = 10^((-70 + 0.691) / 10).  Relative gate: of those,
+ *        z_j > 0.1 (their sum / their number).  loud = -0.691 + 10 log10(the sum of the blocks over both / their number);  -inf when there is none;  NaN when a
+ *        block of the row is not finite (a NaN or an infinity among the samples; such a block passes no gate).
+ *        stats int32 [B, 3]: the blocks, those over the absolute gate, those over both.
+ *     4. Gain.  gain = (float) 10^(min(target - loud, max_gain_db) / 20), formed in fp64 and rounded once;  1.0f where loud is not finite.  target in [-70, 0]
+ *        LUFS, max_gain_db in [0, 60].  loud fp64 [B], gain fp32 [B].
+ *     5. Apply (vs_gain_apply).  y = x gain[b], one fp32 product, for i < n;  y is the bits of x for i >= n and on every row whose gain is exactly 1.0f.
+ *        y == x exactly (in place) is allowed.  16-byte loads and stores where L % 4 == 0 and x, y are 16-byte aligned, 4-byte ones otherwise: the same bits.
+ *     A row's results depend on its own samples only: not on B, the row, L, the padding or the launch shape.
+ *     VS_EINVAL before anything is launched, the outputs untouched: a NULL buffer other than lengths, s outside [800, 4800], B, L or NS < 1, L or NS >= 2^31, a
+ *     coefficient that is not finite, target or max_gain_db out of range, an output overlapping another buffer (y == x apart).  No allocation, no atomics, no
+ *     host synchronisation; samples, lengths, S and gain are read on the device: a captured graph replays on other data by overwriting them.            */
+#define VS_LOUD_THREADS 256
+#define VS_LOUD_MIN_RATE 8000
+#define VS_LOUD_MAX_RATE 48000
+#define VS_LOUD_ABS_GATE 1.1724653045822981e-07
+VS_API int vs_loud_steps(const float *wav, const int64_t *lengths, int64_t B, int64_t L, const double *coef, const double *carry, int s, double *S, int64_t NS,
+                         void *stream);
+VS_API int vs_loud_gate(const double *S, const int64_t *lengths, int64_t B, int64_t NS, int s, double target, double max_gain_db, double *loud, float *gain,
+                        int32_t *stats, void *stream);
+VS_API int vs_gain_apply(const float *x, const float *gain, const int64_t *lengths, float *y, int64_t B, int64_t L, void *stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * a13 grouped / strided Conv1d of the scale discriminator (modules/discriminator.py:55-60) and its gradients.
  *     x: [B, c_in, T], w: [c_out, c_in/groups, k], y / gy: [B, c_out, T_out], T_out = (T + 2*pad - k)/stride + 1.
  *     vs_gconv1d_bwd_weight writes one plane per batch item, gw_planes [B][c_out, c_in/groups, k]; gw = their sum.

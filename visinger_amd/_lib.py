@@ -147,7 +147,11 @@ def lib():
     L.vs_level_gain.argtypes = [_f32p, _f32p, vp, vp, ci, ci, ci, ci, ci, ci, vp, i64, i64, vp]
     L.vs_level_apply.argtypes = [_f32p, vp, vp, ci, _f32p, i64, i64, i64, vp]
     L.vs_peak_limit.argtypes = [_f32p, vp, vp, cf, ci, _f32p, vp, vp, i64, i64, vp]
-    L.vs_expand_states.argtypes = [_f32p, vp, _f32p, i64, i64, i64, i64, ci, ci, vp]
+    cd = ctypes.c_double
+    L.vs_loud_steps.argtypes = [_f32p, vp, i64, i64, ctypes.POINTER(cd), vp, ci, vp, i64, vp]
+    L.vs_loud_gate.argtypes = [vp, vp, i64, i64, ci, cd, cd, vp, vp, vp, vp]
+    L.vs_gain_apply.argtypes = [_f32p, vp, vp, _f32p, i64, i64, vp]
+    L.vs_expand_states.argtypes =[_f32p, vp, _f32p, i64, i64, i64, i64, ci, ci, vp]
     L.vs_make_positions.argtypes = [_f32p, vp, i64, i64, i64, vp]
     L.vs_slice_segments.argtypes = [_f32p, vp, _f32p, i64, i64, i64, i64, vp]
     L.vs_mel2token_to_dur.argtypes = [vp, vp, i64, i64, i64, i64, vp]

@@ -10,6 +10,7 @@ from . import dynamics
 from . import guide_align as guide_align_ops
 from . import guide_correct as guide_correct_ops
 from . import limiter, pitch, pitch_track, resample, sampling, timing
+from . import loudness as loudness_ops
 from . import vibrato as vibrato_ops
 
 
@@ -286,6 +287,26 @@ def _check_vibrato(given, hop_size, items, model):
     return rows, depths
 
 
+def _check_loudness(given, resample_to):
+    """the check of synthesize(loudness=): a dict of loudness.DEFAULTS keys plus the required sample_rate, the model's; the rate the stage measures at --
+    resample_to's output_rate when the call converts, else sample_rate -- is one loudness.check_rate takes.  Returns (the rate it measures at, the DEFAULTS keys
+    given); ValueError otherwise.  Checked on its own like vibrato, not through OPTIONS, behind that table's refusals and before the model is looked at."""
+    opts = A.keys("loudness", given, ("sample_rate", *loudness_ops.DEFAULTS))
+    if "sample_rate" not in opts:
+        raise ValueError(f"loudness must contain sample_rate (the model's), got {sorted(opts)}")
+    loudness_ops.check_args(**opts)
+    rate = opts.pop("sample_rate")
+    if resample_to is not None:
+        if resample_to["sample_rate"] != rate:
+            raise ValueError(f"loudness: sample_rate = {rate!r} is not resample_to's sample_rate = {resample_to['sample_rate']!r} (both are the model's)")
+        try:
+            loudness_ops.check_rate(resample_to["output_rate"])
+        except ValueError as e:
+            raise ValueError(f"loudness measures at resample_to's output_rate: {e}") from None
+        rate = resample_to["output_rate"]
+    return rate, opts
+
+
 def guide_items(items, hop_size, device, max_frames_per_batch=32768, fit=True, level=None, **track):
     """Copies of `items` in which a recording "guide_wav" -- a 1-D float array -- is replaced by "f0": its pitch curve, tracked on the device
     (pitch_track.extract_f0(**track), which needs sample_rate, the model's) in length buckets -- zero-padded, the lengths in a device tensor -- read back and fitted
@@ -508,10 +529,10 @@ def retime_items(items, tempo, device, max_frames_per_batch=32768):
 
 
 class PostChain:
-    """The device stages behind the generator, in their order -- guide dynamics, rate conversion, peak limiter -- built once per synthesize call from its checked
-    option dicts.  A stage whose dict is None is not asked for: nothing changes, it makes no tensor and launches nothing.  The stages run on the batch's own
+    """The device stages behind the generator, in their order -- guide dynamics, rate conversion, loudness normalisation, peak limiter: stages 5 to 8 of 8 in
+    synthesize's list -- built once per synthesize call from its checked option dicts.  A stage whose dict is None is not asked for: nothing changes, it makes no tensor and launches nothing.  The stages run on the batch's own
     stream (behind a graph's replay, outside the capture), before the waveforms are copied to the host: rows B * takes, each frames * hop_size samples long.
-    Each stage's result equals, bit for bit, its wrapper -- match_dynamics(), resample(), limit_peaks(), which say what the keys mean -- applied to the waveform
+    Each stage's result equals, bit for bit, its wrapper -- match_dynamics(), resample(), normalize(), limit_peaks(), which say what the keys mean -- applied to the waveform
     the call returns without that option.  ValueError (synthesize): an option that is not a dict, an unknown key, a value out of range.
     guide_dynamics -- a dict of dynamics.DEFAULTS keys, possibly empty -- makes every item with a level curve sing with that curve's dynamics.
     The curve is the item's "level" -- fp32 mean-square power, one value per frame, 0 = no level there -- given or tracked by the guide pre-pass; after the
@@ -521,11 +542,15 @@ class PostChain:
     resample_to -- a dict with sample_rate (the model's) and output_rate, optionally the converter's quality keywords -- converts the waveforms:
     entry i of the result is then out_length(frames_i * hop_size) samples long (per take); a curve asked back with return_f0 stays per frame.  ValueError also:
     a missing key, a ratio over the converter's table budget.
+    loudness -- (the rate it measures at, a dict of loudness.DEFAULTS keys), as _check_loudness returns it -- brings every row, so every take of
+    an item on its own, to target_lufs: stage 7 of 8, measured at the output rate on what the converter wrote, with the rows' lengths at that rate.  A row
+    shorter than 400 ms or without a block over the gates comes back bit for bit.
     limit -- a dict of limiter.DEFAULTS keys, possibly empty -- holds every waveform under the ceiling: the last step, behind a guide_dynamics
-    boost and resample_to's conversion, which both overshoot, with the rows' lengths at the output rate.  A whole quiet item comes back bit for bit."""
+    boost, resample_to's conversion and a loudness gain, which all overshoot, with the rows' lengths at the output rate.  A whole quiet item comes back bit for
+    bit.  Where the limiter reduces a normalised waveform, the delivered loudness is slightly below target_lufs: by what the reduction takes."""
 
-    def __init__(self, resample_to, guide_dynamics, limit, hop_size, takes):
-        self.dyn, self.lim, self.hop, self.takes = guide_dynamics, limit, hop_size, takes
+    def __init__(self, resample_to, guide_dynamics, limit, hop_size, takes, loudness=None):
+        self.dyn, self.lim, self.hop, self.takes, self.loud = guide_dynamics, limit, hop_size, takes, loudness
         self.rates = None if resample_to is None else (resample_to["sample_rate"], resample_to["output_rate"])
         self.quality = None if resample_to is None else {k: v for k, v in resample_to.items() if k in resample.DEFAULTS}
 
@@ -535,28 +560,31 @@ class PostChain:
 
     def batch(self, frames, levels, T, device):
         """The bundle (apply, tensors) of a batch T frames wide, of items of `frames` frames with the level curves `levels` (None: none).  tensors: what it has put on
-        the device, per take -- the level rows, the rows' lengths at the model's rate (dynamics, converter) and at the output rate (limiter); apply(wav_dev) runs the stages"""
+        the device, per take -- the level rows, the rows' lengths at the model's rate (dynamics, converter) and at the output rate (loudness, limiter); apply(wav_dev) runs the stages"""
         rows = lambda per_item: torch.tensor([v for v in per_item for _ in range(self.takes)], dtype=torch.int64).to(device)
         level = samples = samples_out = None
         if self.dyn is not None and any(lv is not None for lv in levels):
             level = _pad_rows([() if lv is None else lv for lv in levels for _ in range(self.takes)], torch.float32, T).to(device)
         if level is not None or self.rates is not None:
             samples = rows(n * self.hop for n in frames)
-        if self.lim is not None:
+        if self.lim is not None or self.loud is not None:
             samples_out = rows(self.out_samples(n) for n in frames)
         def apply(wav_dev):
             if level is not None:
                 wav_dev = dynamics.match_dynamics(wav_dev.float(), level, self.hop, lengths=samples, **self.dyn)
             if self.rates is not None:
                 wav_dev = resample.resample(wav_dev, *self.rates, lengths=samples, **self.quality)
-            return wav_dev if samples_out is None else limiter.limit_peaks(wav_dev.float().contiguous(), lengths=samples_out, **self.lim)
+            if self.loud is not None:
+                wav_dev = loudness_ops.normalize(wav_dev.float().contiguous(), self.loud[0], lengths=samples_out, **self.loud[1])
+            return wav_dev if self.lim is None else limiter.limit_peaks(wav_dev.float().contiguous(), lengths=samples_out, **self.lim)
         return apply, [t for t in (level, samples, samples_out) if t is not None]
 
 
 @torch.no_grad()
 def synthesize(model, items, hop_size, max_frames_per_batch=32768, noise_scale=1.0, generator=None, equal_tokens=False,
                graphs=None, streams=2, seeds=None, takes=1, first_take=0, voicing="guide", pitch_shift_cents=None, return_f0=False,
-               tempo=None, guide_track=None, guide_align=None, guide_correct=None, resample_to=None, guide_dynamics=None, limit=None, vibrato=None):
+               tempo=None, guide_track=None, guide_align=None, guide_correct=None, resample_to=None, guide_dynamics=None, limit=None, vibrato=None,
+               loudness=None):
     """Run VISinger.forward(infer=True) over length-bucketed batches.  Returns a list of float32 waveforms trimmed to
     each item's own length (frames * hop_size), in the input order.
 
@@ -602,7 +630,7 @@ def synthesize(model, items, hop_size, max_frames_per_batch=32768, noise_scale=1
     per token, read at a note's first token; NaN or None = the call's depth_cents).  Checked next to `voicing`, behind the option dicts below.
 
     The controls, in the order their stages run: four pre-passes on the device, on copies of the items -- the call runs on what they leave, so buckets, `ragged`,
-    graphs and trimming see the new lengths and curves -- then three stages behind the generator, on the batch's own stream.  Each option is None (nothing changes, nothing is launched) or a dict, checked through OPTIONS before the model is looked at and before any launch
+    graphs and trimming see the new lengths and curves -- then four stages behind the generator, on the batch's own stream.  Each option is None (nothing changes, nothing is launched) or a dict, checked through OPTIONS before the model is looked at and before any launch
     (ValueError), in the order resample_to, guide_dynamics, limit, guide_correct, guide_align, guide_track.
       1. guide_track      the pitch (and level) curve of an item's recording "guide_wav" is tracked     -> guide_items
                           (with "path": {...} as a Viterbi path through every frame's lag candidates, pitch_track.extract_f0(path=))
@@ -611,7 +639,12 @@ def synthesize(model, items, hop_size, max_frames_per_batch=32768, noise_scale=1
       4. tempo            and an item's "ph_stretch": the alignment is retimed, the curves warped        -> retime_items
       5. guide_dynamics   items with a "level" curve are sung with its dynamics                          -> PostChain, dynamics.match_dynamics
       6. resample_to      the waveforms are converted to output_rate                                     -> PostChain, resample.resample
-      7. limit            the waveforms are held under a ceiling                                         -> PostChain, limiter.limit_peaks"""
+      7. loudness         every waveform is brought to a target programme loudness in LUFS               -> PostChain, loudness.normalize
+      8. limit            the waveforms are held under a ceiling                                         -> PostChain, limiter.limit_peaks
+    loudness (visinger_amd/loudness.py) is None or a dict of loudness.DEFAULTS keys (target_lufs, max_gain_db) plus the required sample_rate, the
+    model's: mono BS.1770-4 integrated loudness, measured on the device at the rate the waveforms leave at (resample_to's output_rate when given), every take of
+    an item on its own.  It is no row of OPTIONS: checked on its own behind that table's refusals, before the model is looked at.  The limiter stays last and
+    catches what a boost pushes over the ceiling; its reduction then lowers the delivered loudness slightly below target_lufs."""
     sung = any(it.get("guide_wav") is not None for it in items)                  # (no recording: guide_track is not looked at)
     opts = {}
     for name, given in zip(OPTIONS, (resample_to, guide_dynamics, limit, guide_correct, guide_align, guide_track if sung else None)):
@@ -620,6 +653,7 @@ def synthesize(model, items, hop_size, max_frames_per_batch=32768, noise_scale=1
             raise ValueError("an item carries 'level': give guide_dynamics, a dict of dynamics.DEFAULTS keys (possibly empty)")
     if sung and guide_track is None:
         raise ValueError("an item carries 'guide_wav': give guide_track, a dict of pitch_track.extract_f0 keywords with sample_rate")
+    loud = None if loudness is None else _check_loudness(loudness, opts["resample_to"])
     device = next(model.parameters()).device
     if sung:
         level = None if opts["guide_dynamics"] is None else opts["guide_dynamics"].get("half_width", dynamics.DEFAULTS["half_width"])
@@ -653,7 +687,7 @@ def synthesize(model, items, hop_size, max_frames_per_batch=32768, noise_scale=1
     keys = [len(it["text_tokens"]) for it in items] if equal_tokens else None
     if any(guided):
         keys = [(g, k) for g, k in zip(guided, keys if keys is not None else [0] * len(items))]
-    chain = PostChain(opts["resample_to"], opts["guide_dynamics"], opts["limit"], hop_size, takes)
+    chain = PostChain(opts["resample_to"], opts["guide_dynamics"], opts["limit"], hop_size, takes, loudness=loud)
     rotation = StreamRotation(streams) if (graphs is None and streams and streams > 1) else None
     pending = []                                 # (item indices, device waveforms, device f0, event) of the batches in flight
 
