@@ -146,12 +146,12 @@ def figures(got, ref, S):
     return err, per_s, scaled
 
 
-def assert_close(got, ref, S, what="", *, bound=None, F=None):
+def assert_close(got, ref, S, what="", *, bound=None, F=None, tag="SPLIT3REF"):
     """Element-wise over ALL elements: |got - ref| <= F_SPLIT * 2^-24 * S (or `bound`, an array: the paired kinds and the moving-scale group state
-    theirs), everything finite.  Prints `SPLIT3REF <what>: per_S <..> scaled <..>` before it asserts; the message names the worst index and how many
-    elements exceed the bound.  -> (per_S, scaled)"""
+    theirs), everything finite.  Prints `SPLIT3REF <what>: per_S <..> scaled <..>` (`tag`: another first word -- tests/exact_reference.py) before it
+    asserts; the message names the worst index and how many elements exceed the bound.  -> (per_S, scaled)"""
     err, per_s, scaled = figures(got, ref, S)
-    print(f"SPLIT3REF {what}: per_S {per_s:.3f} scaled {scaled:.4f}")
+    print(f"{tag} {what}: per_S {per_s:.3f} scaled {scaled:.4f}")
     g = to_np(got)
     assert np.isfinite(g).all(), f"{what}: {int((~np.isfinite(g)).sum())} non-finite elements"
     bound = (F_SPLIT if F is None else F) * EPS32 * S if bound is None else np.asarray(bound, np.float64)
